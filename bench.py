@@ -8,7 +8,12 @@ all queries of the step / max-over-ranks step time.
 Launch: ``python bench.py`` (1 GPU), ``torchrun --nproc-per-node N bench.py --gpus N``, or
 ``python bench.py --gpus N`` (spawns the N ranks itself through torch.distributed.run, as a
 child process started before anything touches the GPU).  Rank 0 prints ONE JSON line.
-Extra objects: ``roofline`` (dominant kernel, HIP events on its stream), ``cpu_baseline``
+
+A plain run does the headline only: set-up, ``--warmup`` + ``--steps`` decode steps, the result
+line (``value``, ``ms_per_step``, and ``roofline`` / ``step_time_events`` from the HIP events of
+those same steps).  ``--dump-outputs DIR`` also writes the last step's volume (``DIR/sdf.npy``,
+a fixed seeded sample when it is large); the inputs are seeded, so two builds compare value for
+value.  ``--full`` adds every other leg as objects of the same line: ``decode_b1``, ``cpu_baseline``
 (oracle/ref_cpu.py fp32 on this host's cores, bounded sample), ``ddpm`` (1000-step sampling
 of 8 latents, steps/s, + config 3 end to end), ``config5``, ``train`` (config 2), ``mc``,
 ``autodecoder``.
@@ -35,6 +40,8 @@ import torch.distributed as dist  # noqa: E402
 
 FLOPS_PER_QUERY = 2 * (3 * 512 + 2 * 512 * 512 + 512 * 253 + 256 * 512 + 3 * 512 * 512 + 512)
 PEAK_TFLOPS = {"bf16": 2516.6, "fp16": 2516.6, "fp32": 157.3}   # MI355X dense (MICROARCH guide)
+DUMP_MAX_ELEMS = 4 * 1024 * 1024      # --dump-outputs: 16 MB of float32
+DUMP_SEED = 20240229
 
 
 def parse():
@@ -65,7 +72,33 @@ def parse():
                          "decode is a dec_fs_kernel launch of another size in a profile)")
     ap.add_argument("--shapes-per-group", type=int, default=0,
                     help="multi-GPU decode: shapes per gather group (0: ceil(B/8))")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline decode steps also run every other leg (decode_b1, "
+                         "ddpm + config 3, mc, config5, train, autodecoder, the CPU baselines; "
+                         "each has its own --no-* switch); without it only the headline runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/sdf.npy "
+                         "(float32): the whole (batch, grid, grid, grid) volume when it has at "
+                         f"most {DUMP_MAX_ELEMS} values, else that many of them at fixed, seeded "
+                         "flat indices (in ascending order)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(dirname: str, out: torch.Tensor) -> None:
+    """``--dump-outputs``: the decoded volume of the last timed step (``out``, what a caller of
+    ``decode`` receives) as ``sdf.npy``; a volume above ``DUMP_MAX_ELEMS`` values is sampled at
+    flat indices drawn once from a seeded CPU generator, the same for every run of a shape."""
+    import numpy as np
+    flat = out.reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "sdf.npy"), flat.float().cpu().numpy())
 
 
 def host_cores() -> int:
@@ -699,10 +732,17 @@ def main():
     peak = PEAK_TFLOPS[args.dtype]
     traffic, traffic_src = decoder_traffic(qpl)
 
-    # SURVEY §8(d)'s single-shape headline: ONE shape's 256^3 grid (16.8 M queries), same kernel
     leg("rank breakdown done")
-    b1 = bench_decode_b1(args, rank, world, dev, group, decoder, desc, gen)
-    leg("decode_b1 done")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+        leg("outputs written")
+    # everything below the headline runs under --full only
+    b1 = None
+    if args.full:
+        # SURVEY §8(d)'s single-shape headline: ONE shape's 256^3 grid (16.8 M queries), same
+        # kernel
+        b1 = bench_decode_b1(args, rank, world, dev, group, decoder, desc, gen)
+        leg("decode_b1 done")
 
     res = None
     if rank == 0:
@@ -729,30 +769,32 @@ def main():
                          "queries_per_launch": qpl, "avg_launch_ms": kms,
                          "launches_per_step": len(slab.events) // max(1, args.steps)},
             "step_time_events": event_summary(step_ev),
-            "decode_b1": b1,
         }
+        if args.full:
+            res["decode_b1"] = b1
         if multi is not None:
             res["multi_gpu"] = multi
-    if not args.no_ddpm:
+    full = args.full
+    if full and not args.no_ddpm:
         leg("ddpm")
         r = bench_ddpm(args, rank, world, dev, group, gen, decoder)
         if rank == 0:
             res["ddpm"] = r
-    if rank == 0 and not args.no_mc:
+    if full and rank == 0 and not args.no_mc:
         leg("mc")
         res["mc"] = bench_mc(out[0], args)
-    if not args.no_config5:
+    if full and not args.no_config5:
         leg("config5")
         res_c5 = config5(args, rank, world, dev, group, gen)
         if rank == 0:
             res["config5"] = res_c5
-    if rank == 0 and not args.no_train:
+    if full and rank == 0 and not args.no_train:
         leg("train")
         res["train"] = bench_train(args, dev, gen)
-    if rank == 0 and not args.no_autodecoder:
+    if full and rank == 0 and not args.no_autodecoder:
         leg("autodecoder")
         res["autodecoder"] = bench_autodecoder(args, dev)
-    if rank == 0 and not args.no_cpu:
+    if full and rank == 0 and not args.no_cpu:
         res["cpu_baseline"] = cpu_baseline_decode(N, args.cpu_seconds)
         if "ddpm" in res:
             res["ddpm"]["cpu_baseline"] = cpu_baseline_sampling(min(5.0, args.cpu_seconds),

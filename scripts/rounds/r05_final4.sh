@@ -16,7 +16,7 @@ step() {   # name timeout cmd...
 
 TAILN=4 step pytest_gpu 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread
 step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
-TAILN=2 step bench 600 python -u bench.py
-TAILN=3 step rocprof 900 rocprofv3 --kernel-trace --stats -d $O/prof -o bench --output-format csv -- python3 bench.py
+TAILN=2 step bench 600 python -u bench.py --full
+TAILN=3 step rocprof 900 rocprofv3 --kernel-trace --stats -d $O/prof -o bench --output-format csv -- python3 bench.py --full
 find $O/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/bench_kernel_stats.csv
 head -12 $O/bench_kernel_stats.csv

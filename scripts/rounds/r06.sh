@@ -44,8 +44,8 @@ case $B in
     LDM_SDF_LIB=$LIB/libldm_sdf_debug.so TAILN=4 step pytest_gpu_debug 900 $PYT tests -m gpu -k "not test_native_library_is_loaded"
     ;;
   bench)
-    TAILN=2 step bench 600 python -u bench.py
-    TAILN=3 step rocprof 900 rocprofv3 --kernel-trace --stats -d $O/prof -o bench --output-format csv -- python3 bench.py
+    TAILN=2 step bench 600 python -u bench.py --full
+    TAILN=3 step rocprof 900 rocprofv3 --kernel-trace --stats -d $O/prof -o bench --output-format csv -- python3 bench.py --full
     find $O/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/bench_kernel_stats.csv
     head -12 $O/bench_kernel_stats.csv
     ;;
@@ -63,8 +63,8 @@ case $B in
   multirank)
     # the N > 1 flow of bench.py (z-slab gathers, rank-0 legs, barriers) rehearsed on one GPU:
     # 2 ranks on cuda:0 over gloo (timings meaningless: both ranks share the device)
-    LDM_BENCH_BACKEND=gloo LDM_BENCH_TRACE=1 LDM_BENCH_WATCHDOG=150 TAILN=40 step bench_gloo2 300 python -u bench.py --gpus 2 --steps 1 --warmup 1 --no-cpu --no-ddpm --no-config5 --train-steps 5 --ad-steps 1
-    LDM_BENCH_BACKEND=gloo LDM_BENCH_TRACE=1 LDM_BENCH_WATCHDOG=170 TAILN=40 step bench_gloo2_all 300 python -u bench.py --gpus 2 --steps 1 --warmup 1 --no-cpu --train-steps 5 --ad-steps 1
+    LDM_BENCH_BACKEND=gloo LDM_BENCH_TRACE=1 LDM_BENCH_WATCHDOG=150 TAILN=40 step bench_gloo2 300 python -u bench.py --full --gpus 2 --steps 1 --warmup 1 --no-cpu --no-ddpm --no-config5 --train-steps 5 --ad-steps 1
+    LDM_BENCH_BACKEND=gloo LDM_BENCH_TRACE=1 LDM_BENCH_WATCHDOG=170 TAILN=40 step bench_gloo2_all 300 python -u bench.py --full --gpus 2 --steps 1 --warmup 1 --no-cpu --train-steps 5 --ad-steps 1
     ;;
   adam)
     # the AdamW tile A/B: correctness first, then kernel time and the config-2 step per library
