@@ -46,15 +46,17 @@ def _denoiser():
 def test_config2_train_step_bf16_batch1000(dev):
     """Config 2's step: 1000 latents, batch 1000, bf16 weights + matrix-core GEMMs, vs the fp64
     oracle's autograd on the same (x0, t, eps): loss within 1e-3 relative, every gradient
-    (whole tensor) at cosine >= 0.999 and norm within 2 %."""
+    (whole tensor) at cosine >= 0.999 and norm within 2 %; and loss and every gradient
+    ELEMENT-WISE against the bf16-operand emulation (tests/denoiser_emulation.py) at its
+    tolerance, TOL.  The inputs are the seed-2024 draw with the last sample's noise at 4 sigma
+    (denoiser_emulation.inputs), so that a step that loses the last live row lands >= 4 x TOL
+    away even among 1000 samples (tests/test_train_emulation.py)."""
     import ldm_sdf
     from oracle import ref_cpu as R
+    from tests import denoiser_emulation as E
     model, p = _denoiser()
     model.to_device(dev)
-    g = torch.Generator().manual_seed(2024)
-    x0 = torch.randn(1000, 256, generator=g) * 0.5
-    t = torch.randint(0, 1000, (1000,), generator=g, dtype=torch.int32)
-    eps = torch.randn(1000, 256, generator=g)
+    x0, t, eps = E.inputs(1000, 256, E.CONFIG2_CASE[2])
     loss, grads = ldm_sdf.train_step(model, ldm_sdf.DDPMSchedule(), x0.to(dev), t.to(dev),
                                      eps.to(dev), dtype="bf16")
     emb = torch.from_numpy(R.timestep_embedding_table(1000, 128)).double()
@@ -70,6 +72,8 @@ def test_config2_train_step_bf16_batch1000(dev):
         print(f"config2 grad {k}: cos {cos:.6f} norm rel {rel:.2e}")
         assert cos >= 0.999, (k, cos)
         assert rel <= 2e-2, (k, rel)
+    em_loss, em = E.fused_reference(E.CONFIG2_CASE)
+    E.check_against(float(loss), {k: v.cpu() for k, v in grads.items()}, em_loss, em, "config2")
 
 
 def test_config3_sample8_then_decode128(dev):

@@ -3,10 +3,15 @@ ldm_denoiser_fwd (per-sample t) / ldm_denoiser_bwd / ldm_denoiser_train_step /
 ldm_q_sample_loss / ldm_adamw_multi, called through ctypes.
 
 References:
-  * a bf16-operand emulation of the oracle (oracle/ref_cpu.py's network with every GEMM operand
-    rounded to bf16 as the kernels round it, fp64 arithmetic otherwise): the forward output
-    agrees to <= 2e-3 relative to its scale (rounding-boundary flips of single operands and
-    fp32 accumulation order are all that differ);
+  * a bf16-operand emulation of the oracle (tests/denoiser_emulation.py: oracle/ref_cpu.py's
+    network and its backward with every GEMM operand rounded to bf16 as the kernels round it,
+    fp64 arithmetic otherwise): the forward output agrees to <= 2e-3 relative to its scale
+    (rounding-boundary flips of single operands and fp32 accumulation order are all that
+    differ); the loss, EVERY gradient and dx agree ELEMENT-WISE (max|dev| / max|ref| per tensor)
+    at denoiser_emulation.TOL = 4 x the CPU noise floor of tests/test_train_emulation.py, which
+    also shows that a dropped sample, a zeroed gradient row, a skipped dtemb K-segment and an
+    unmasked padding row each land >= 4 x TOL away (the whole-tensor checks below let all four
+    through);
   * the fp64 oracle itself (unrounded weights): loss within 1e-3 relative, every gradient at
     cosine >= 0.999 and norm within 2 % (bf16 operand rounding), as the ldm_linear bf16 path;
   * the modular fwd -> q_sample_loss -> bwd sequence against the fused step on the same
@@ -20,6 +25,8 @@ import math
 import numpy as np
 import pytest
 import torch
+
+from tests import denoiser_emulation as E
 
 pytestmark = pytest.mark.gpu
 
@@ -44,25 +51,6 @@ def net():
     return MLPDenoiser(params=params), p
 
 
-def _bf(x):
-    return x.float().bfloat16().double()
-
-
-def _emulated_forward(p, x, t, emb):
-    """oracle network with GEMM operands rounded to bf16 (weights and activations), fp64
-    otherwise; the residual stream stays unrounded as on the device."""
-    e = emb[t.long()]
-    a_t = _bf(e) @ _bf(p.Wt1).T + p.bt1.float().double()
-    u = a_t * torch.sigmoid(a_t)
-    temb = _bf(u) @ _bf(p.Wt2).T + p.bt2.float().double()
-    h = _bf(x) @ _bf(p.Win).T + p.bin.float().double()
-    for k in range(p.n_blocks):
-        W = _bf(p.Wblk[k])
-        a = _bf(h) @ W[:, :p.H].T + _bf(temb) @ W[:, p.H:].T + p.bblk[k].float().double()
-        h = h + a * torch.sigmoid(a)
-    return _bf(h) @ _bf(p.Wout).T + p.bout.float().double()
-
-
 def _inputs(B, seed):
     g = torch.Generator().manual_seed(seed)
     x0 = torch.randn(B, 256, generator=g) * 0.5
@@ -84,7 +72,7 @@ def test_denoiser_fwd_per_sample_t(dev, net, B):
     out = torch.empty(B, 256, device=dev)
     ops.denoiser_fwd(desc, x0.to(dev), t.to(dev), ws, out)
     emb = torch.from_numpy(R.timestep_embedding_table(1000, 128)).double()
-    want = _emulated_forward(p, x0.double(), t, emb)
+    want = E.forward(p, x0, t, emb)["eps_hat"]
     scale = float(want.abs().max())
     err = float((out.cpu().double() - want).abs().max()) / scale
     print(f"B={B}: fwd rel err vs bf16-emulated oracle {err:.2e}")
@@ -124,6 +112,123 @@ def test_train_step_fused_vs_oracle(dev, net, B):
         rel = abs(float(got.norm()) - float(w.norm())) / float(w.norm())
         print(f"B={B} {k}: cos {cos:.6f} norm rel {rel:.2e}")
         assert cos >= 0.999 and rel <= 2e-2, (k, cos, rel)
+
+
+def _device_fused_step(dev, case, poison=False):
+    """ldm_denoiser_train_step (the launches) on a case's inputs, gradients pre-filled with NaN;
+    ``poison``: the workspace holds 0xFF bytes (NaN as bf16 and as fp32) before its init."""
+    import ctypes as C
+    import ldm_sdf
+    from ldm_sdf import _capi as capi, ops
+    net_shape, B, seed = case
+    p = E.oracle_net(net_shape)[0]
+    model = E.model_of(p)
+    model.to_device(dev)
+    desc = model.device_pack("bf16", dev, with_tables=False)["desc"]
+    sd = ldm_sdf.DDPMSchedule().device(dev)
+    x0, t, eps = E.inputs(B, p.D, seed)
+    grads = {n: torch.full_like(model.params[n], float("nan")) for n in model.names()}
+    loss = torch.full((1,), float("nan"), device=dev)
+    ws = ops.train_workspace(desc, B, dev)
+    if poison:
+        ws.fill_(0xFF)
+        capi.check(capi.load().ldm_denoiser_train_ws_init(C.byref(desc), B, ws.data_ptr(),
+                                                          capi.stream_handle(dev)),
+                   "ldm_denoiser_train_ws_init")
+    ops.denoiser_train_step(desc, sd["desc"], x0.to(dev), eps.to(dev), t.to(dev), ws,
+                            model.grads_struct(grads), loss)
+    torch.cuda.synchronize()
+    assert ops.train_step_last_form() == "launches"
+    return float(loss), {n: g.cpu() for n, g in grads.items()}
+
+
+DEFAULT_CASES = [c for c in E.FUSED_CASES if c[0] == E.DEFAULT_NET and c != E.CONFIG2_CASE]
+OTHER_CASES = [c for c in E.FUSED_CASES if c[0] != E.DEFAULT_NET]
+
+
+@pytest.mark.parametrize("case", DEFAULT_CASES, ids=[f"B{c[1]}" for c in DEFAULT_CASES])
+def test_train_step_elementwise_vs_emulation(dev, case):
+    """The fused step's loss and every gradient, ELEMENT-WISE against the bf16-operand emulation
+    (tests/denoiser_emulation.py) at denoiser_emulation.TOL (weights 1.2e-2, biases 4e-3, loss
+    1.2e-5 of the tensor's largest magnitude: 4 x the CPU noise floor, and >= 4 x below what a
+    dropped sample, a zeroed row, a skipped dtemb segment or an unmasked padding row moves --
+    tests/test_train_emulation.py).  B = 1: one live row in a 64-row pad; 37: a ragged band;
+    65: the second 64-row band and the third 32-row block hold one live row; 200; 1000: config
+    2's size, the only one at which the dtemb launch takes its 128-deep tile and the grouped
+    launches their large-batch tile choice.
+
+    Measured on the MI355X, largest deviation per tensor kind (weights / biases / loss):
+        B = 1      3.0e-3 / 2.3e-4 / 5.9e-8      B = 37     3.1e-3 / 9.0e-4 / 9.4e-7
+        B = 65     1.2e-3 / 5.6e-4 / 2.6e-7      B = 200    9.2e-4 / 5.8e-4 / 6.6e-7
+        B = 1000   4.0e-3 / 3.4e-4 / 5.8e-7      config 2   1.2e-3 / 2.7e-4 / 2.9e-7
+        (1,256,128,64) 4.1e-4 / 2.0e-4 / 9.3e-8  (2,512,64,128) 5.3e-4 / 2.5e-4 / 8.8e-7
+        (8,256,256,64) 4.5e-4 / 1.9e-4 / 6.8e-7  poisoned workspace: the fresh one's figures
+        modular B = 65: 6.8e-4 / 3.4e-4, dx 2.0e-4;  B = 200: 7.0e-4 / 3.2e-4, dx 2.9e-4
+    (B = 1 and B = 1000, where the 4-sigma last sample dominates the largest elements: one
+    flipped bf16 tie in a row of g shows at nearly full size, 2^-8 = 3.9e-3)."""
+    got_loss, got = _device_fused_step(dev, case)
+    want_loss, want = E.fused_reference(case)
+    E.check_against(got_loss, got, want_loss, want, f"B={case[1]}")
+
+
+@pytest.mark.parametrize("case", OTHER_CASES,
+                         ids=[f"nb{c[0][0]}-H{c[0][1]}-D{c[0][2]}-TE{c[0][3]}" for c in OTHER_CASES])
+def test_train_step_elementwise_other_networks(dev, case):
+    """The networks test_gpu_train_dag.py only compares DAG == launches on -- (n_blocks, H, D,
+    TE) = (1, 256, 128, 64), (2, 512, 64, 128), (8, 256, 256, 64) at B = 200 -- element-wise
+    against the emulation, same tolerance."""
+    got_loss, got = _device_fused_step(dev, case)
+    want_loss, want = E.fused_reference(case)
+    E.check_against(got_loss, got, want_loss, want, E.case_id(case))
+
+
+@pytest.mark.parametrize("B", [37, 65])
+def test_train_step_poisoned_workspace(dev, B):
+    """The step must not depend on what its workspace held: padding rows of every bf16 operand
+    are written (as zero) by their producers (denoiser_train.hip's header), and a fresh zeroed
+    allocation would hide a producer that does not.  The workspace is filled with 0xFF bytes
+    (NaN as bf16 and as fp32) and then initialised as any workspace is; everything must be
+    finite and within the element-wise tolerance."""
+    case = (E.DEFAULT_NET, B, 100 + B)
+    got_loss, got = _device_fused_step(dev, case, poison=True)
+    assert math.isfinite(got_loss)
+    want_loss, want = E.fused_reference(case)
+    E.check_against(got_loss, got, want_loss, want, f"poisoned ws B={B}")
+
+
+@pytest.mark.parametrize("case", E.MODULAR_CASES, ids=[f"B{c[1]}" for c in E.MODULAR_CASES])
+def test_modular_elementwise_vs_emulation(dev, case):
+    """denoiser_fwd -> q_sample_loss -> denoiser_bwd: x_t is the emulation's bit for bit (two
+    rounded products, one rounded sum), and every gradient and dx agree element-wise with the
+    emulation fed the same x_t and the same fp32 deps (there bout is the column sum of deps
+    itself)."""
+    import ldm_sdf
+    from ldm_sdf import ops
+    net_shape, B, seed = case
+    p, emb, sab, s1mab = E.oracle_net(net_shape)
+    model = E.model_of(p)
+    model.to_device(dev)
+    desc = model.device_pack("bf16", dev, with_tables=False)["desc"]
+    sd = ldm_sdf.DDPMSchedule().device(dev)
+    x0, t, eps = E.inputs(B, p.D, seed)
+    xt = torch.empty(B, p.D, device=dev)
+    ops.q_sample_loss(sd["desc"], eps.to(dev), x0=x0.to(dev), t=t.to(dev), xt_out=xt)
+    assert torch.equal(xt.cpu(), E.q_sample_f32(sab, s1mab, x0, eps, t))
+    ws = ops.train_workspace(desc, B, dev)
+    eps_hat = torch.empty(B, p.D, device=dev)
+    ops.denoiser_fwd(desc, xt, t.to(dev), ws, eps_hat)
+    loss, deps = torch.empty(1, device=dev), torch.empty(B, p.D, device=dev)
+    ops.q_sample_loss(sd["desc"], eps.to(dev), eps_hat=eps_hat, loss_out=loss, grad_out=deps)
+    grads = {n: torch.full_like(model.params[n], float("nan")) for n in model.names()}
+    dx = torch.full((B, p.D), float("nan"), device=dev)
+    ops.denoiser_bwd(desc, ws, deps, model.grads_struct(grads), dx)
+    torch.cuda.synchronize()
+    got = {n: g.cpu() for n, g in grads.items()}
+    got["dx"] = dx.cpu()
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    want_eps_hat, want = E.fwd_bwd(p, emb, xt.cpu(), t, deps.cpu())
+    assert E.rel_dev(eps_hat.cpu(), want_eps_hat) <= 2e-3
+    E.check_against(None, got, None, want, f"modular B={B}")
 
 
 def test_modular_fwd_bwd_matches_fused(dev, net):
