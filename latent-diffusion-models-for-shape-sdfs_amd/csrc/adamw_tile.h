@@ -1,4 +1,4 @@
-// One 64 x 64 tile of the multi-tensor AdamW update (ldm_adamw_multi, denoiser_train.hip), shared
+// One 64 x 64 tile of the multi-tensor AdamW update (ldm_adamw_multi, adamw_multi.hip), shared
 // with the persistent training-step kernel (train_dag.hip) so both update every parameter with
 // the same instructions (the update is ldm_adamw_step's, operation for operation: ddpm_common.h
 // adamw_update).  The transposed bf16 copy goes through an LDS tile so its stores are 32-byte

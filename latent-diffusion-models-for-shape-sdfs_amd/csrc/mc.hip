@@ -148,12 +148,10 @@ constexpr McTables kMcHost = make_mc_tables();
 __constant__ McTables kMc = make_mc_tables();
 
 // ------------------------------------------------------------------------------ kernels
-// points per thread of the scan-chunk passes (a multiple of 8; MC_PER A/B builds), a chunk =
-// 256 threads x kPer points
-#ifndef MC_PER
-#define MC_PER 16
-#endif
-constexpr int kPer = MC_PER;
+// points per thread of the scan-chunk passes (a multiple of 8), a chunk = 256 threads x kPer
+// points.  16: 8 and 32 measured 0.139 / 0.146 ms per mesh against 0.130 (DESIGN.md §10,
+// profiles/r06ab).
+constexpr int kPer = 16;
 constexpr int kChunk = 256 * kPer;
 static_assert(kPer % 8 == 0 && kPer <= 32, "whole 16-byte code vectors; a 32-bit cube mask");
 
@@ -446,13 +444,10 @@ __global__ __launch_bounds__(256) void mc_vertices_kernel(const float* __restric
 // can reference (its 12 edges, owned by corners 0..6) is formed from ONE round of 14
 // independent gathers (code and vofs of the 7 owner corners), kept in LDS per thread, and the
 // triangles are read off the table.
-// MC_FACES_PAIR (round 6): a thread takes its cubes with triangles two at a time, from a bit
-// mask, with both cubes' 28 gathers issued before either is used.  The earlier form walked the
-// thread's 16 points in order and gathered inside the walk: a wave paid one serial round trip
-// for every point index at which ANY of its lanes had a cube, up to 16 per wave.
-#ifndef MC_FACES_PAIR
-#define MC_FACES_PAIR 1
-#endif
+// A thread takes its cubes with triangles two at a time, from a bit mask, with both cubes' 28
+// gathers issued before either is used: walking the thread's 16 points in order and gathering
+// inside the walk cost a wave one serial round trip for every point index at which ANY of its
+// lanes had a cube, up to 16 per wave: faces 41.0 -> 37.9 us (profiles/r06z).
 __device__ __forceinline__ void mc_gather_owners(const unsigned short* __restrict__ code,
                                                  const int32_t* __restrict__ vofs, int64_t p,
                                                  int64_t N, int64_t NN, unsigned (&oc)[7],
@@ -503,41 +498,28 @@ __global__ __launch_bounds__(256) void mc_faces_kernel(int N, const unsigned sho
     if (nt == 0) return;
     const int64_t p0 = (int64_t)blockIdx.x * kChunk + threadIdx.x * kPer;
     int* ev = &s_ev[0][threadIdx.x];
-    if (MC_FACES_PAIR) {
-        unsigned am = 0;
+    unsigned am = 0;
 #pragma unroll
-        for (int q = 0; q < kPer; ++q) am |= (ntri_of(c[q]) ? 1u : 0u) << q;
-        // the first triangle of the cube at point q: the thread's offset + the counts before q
-        auto first = [&](int q) {
-            int f = off;
+    for (int q = 0; q < kPer; ++q) am |= (ntri_of(c[q]) ? 1u : 0u) << q;
+    // the first triangle of the cube at point q: the thread's offset + the counts before q
+    auto first = [&](int q) {
+        int f = off;
 #pragma unroll
-            for (int u = 0; u < kPer; ++u) f += u < q ? ntri_of(c[u]) : 0;
-            return f;
-        };
-        while (am) {
-            const int qa = __builtin_ctz(am);
-            am &= am - 1u;
-            const bool hb = am != 0u;
-            const int qb = hb ? __builtin_ctz(am) : qa;
-            if (hb) am &= am - 1u;
-            unsigned oa[7], ob[7];
-            int va[7], vb[7];
-            mc_gather_owners(code, vofs, p0 + qa, N, NN, oa, va);   // a cube with triangles:
-            mc_gather_owners(code, vofs, p0 + qb, N, NN, ob, vb);   // every owner in bounds
-            mc_emit_cube(oa, va, ev, s_tri, first(qa), faces);
-            if (hb) mc_emit_cube(ob, vb, ev, s_tri, first(qb), faces);
-        }
-        return;
-    }
-    for (int q = 0; q < kPer; ++q) {
-        const int ntq = ntri_of(c[q]);
-        if (!ntq) continue;
-        const int64_t p = p0 + q;            // a cube with triangles: every owner is in bounds
-        unsigned oc[7];
-        int ov[7];
-        mc_gather_owners(code, vofs, p, N, NN, oc, ov);
-        mc_emit_cube(oc, ov, ev, s_tri, off, faces);
-        off += ntq;
+        for (int u = 0; u < kPer; ++u) f += u < q ? ntri_of(c[u]) : 0;
+        return f;
+    };
+    while (am) {
+        const int qa = __builtin_ctz(am);
+        am &= am - 1u;
+        const bool hb = am != 0u;
+        const int qb = hb ? __builtin_ctz(am) : qa;
+        if (hb) am &= am - 1u;
+        unsigned oa[7], ob[7];
+        int va[7], vb[7];
+        mc_gather_owners(code, vofs, p0 + qa, N, NN, oa, va);   // a cube with triangles:
+        mc_gather_owners(code, vofs, p0 + qb, N, NN, ob, vb);   // every owner in bounds
+        mc_emit_cube(oa, va, ev, s_tri, first(qa), faces);
+        if (hb) mc_emit_cube(ob, vb, ev, s_tri, first(qb), faces);
     }
 }
 

@@ -94,12 +94,10 @@ __device__ __forceinline__ void load_row(float (&w)[NJ][8], const void* W, int r
 // [B][K] fp32 activations -> LDS.  The activations were written by other workgroups in this
 // launch, so EVERY load of them is an agent-scope relaxed 8-byte load (global_load_dwordx2 sc1:
 // bypasses this CU's L1, served coherently; Guideline 16 table row 1), 16 in flight per
-// thread: one round trip for B*K <= 8192 (B=8, K=1024).
+// thread: one round trip for B*K <= 8192 (B=8, K=1024); 8 took two (round 1; the loop at 16 is
+// what profiles/r01g measured).
 typedef unsigned long long u64;
-#ifndef LDM_STAGE_IN_FLIGHT
-#define LDM_STAGE_IN_FLIGHT 16
-#endif
-constexpr int kStageInFlight = LDM_STAGE_IN_FLIGHT;   // 8-B loads per thread per round
+constexpr int kStageInFlight = 16;   // 8-B loads per thread per round
 template <int NT = 256>
 __device__ __forceinline__ void stage(float* xs, const float* X, int n2) {
     constexpr int U = kStageInFlight * 256 / NT;
@@ -481,11 +479,8 @@ __device__ __forceinline__ void publish_tagged(u64* g, float v, unsigned tag) {
 
 // n granules -> xs[0..n), every thread granules tid, tid + NT, ... (all loads issued before any
 // tag test).  Returns false (and sets the status word) if a granule never arrives.
-// Re-polls a missing granule back to back (LDM_GRAN_SLEEP = 0): measured at B = 8, 74.5k steps/s
-// vs 72.0-72.7k with s_sleep 1 and 64.3k with s_sleep 3 (profiles/r03l/ab_sleep.log).
-#ifndef LDM_GRAN_SLEEP
-#define LDM_GRAN_SLEEP 0
-#endif
+// Re-polls a missing granule back to back, no sleep: measured at B = 8, 74.5k steps/s vs
+// 72.0-72.7k with s_sleep 1 and 64.3k with s_sleep 3 (profiles/r03l/ab_sleep.log).
 template <int NT, int U>
 __device__ __forceinline__ bool stage_tagged(float* xs, const u64* G, int n, unsigned tag,
                                              unsigned* status, unsigned limit) {
@@ -514,9 +509,6 @@ __device__ __forceinline__ bool stage_tagged(float* xs, const u64* G, int n, uns
                         good = false;
                         break;
                     }
-#if LDM_GRAN_SLEEP > 0
-                    __builtin_amdgcn_s_sleep(LDM_GRAN_SLEEP);
-#endif
                     t[u] = __hip_atomic_load(G + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 xs[i] = __builtin_bit_cast(float, (unsigned)t[u]);
@@ -533,120 +525,48 @@ constexpr int kRepWaves = 8;      // 2 waves per SIMD: 4 rows of each layer per 
 // all its layers -- 0 own granules landed, 1 the workgroup's staging barrier (the slowest wave's
 // granules), 2 the row dot products, 3 the reduce-scatter, 4 epilogue + publish -- and writes
 // them at its end (g_sl_stamp[workgroup][wave]); slot 5 counts the layers.
-// Diagnostic builds only (-DSL_STAMP=1).  Round 5 shipped them ON because the stamped build ran
-// 86.5-88.2k steps/s at B = 8 against 72.0-74.4k without; its explanation (index products in
-// SALU instead of VALU) was wrong -- those v_mul_lo_u32 sit in the barrier form's arrival code,
-// which the tagged hand-offs never run.  Round 6 found the real difference in the assembly: both
-// builds SPILLED (116-132 bytes of scratch at 255-256 VGPRs), and each step reloaded 5-6 of a
-// residual block's register-resident weight vectors from scratch, one serial
-// scratch_load + s_waitcnt vmcnt(0) after another; the stamps merely moved one reload.  The fix
-// is SL_LDSBLK below: no spills at all, with or without stamps (tests/test_sampler_codegen.py
-// pins it).
+// Diagnostic builds only (-DSL_STAMP=1): the product kernel carries no stamp code at all, and
+// neither build has any scratch (tests/test_sampler_codegen.py pins both).
 #ifndef SL_STAMP
 #define SL_STAMP 0
 #endif
-// Residual blocks whose weights live in LDS instead of registers (the LAST SL_LDSBLK blocks):
+// Residual blocks whose weights live in LDS instead of registers (the LAST kLdsBlocks blocks):
 // the 4 blocks' register-resident weights (128 VGPRs) + the loop's state overflowed the 256
 // VGPRs a wave has at 2 waves per SIMD, so the compiler spilled weight vectors and reloaded them
 // serially every step.  One block in LDS (64 KiB per workgroup, read as 8 ds_read_b128 per wave
-// per step) frees 32 VGPRs: no scratch at all.  Same arithmetic (the
-// lane's 8 bf16 weights, the same fma chain), so the loop stays bit-identical to the graph path.
-#ifndef SL_LDSBLK
-#define SL_LDSBLK 1
-#endif
+// per step) frees 32 VGPRs: no scratch at all (profiles/r06c).  Same
+// arithmetic (the lane's 8 bf16 weights, the same fma chain), so the loop stays bit-identical to
+// the graph path.
+constexpr int kLdsBlocks = 1;
 // After a layer's publish: the publishing store stays ahead of the next layer's granule polls
-// in issue order (a scheduling barrier), and the wave sleeps one interval (64 cycles) before it
-// starts polling -- fewer polls hit the lines the other producers are still writing (the
-// pause's length: SL_PUBSLEEP below).  What the
-// round-5 stamps did by accident (their mark after the publish: SL_MARKS = 16 alone carried the
-// whole gain, profiles/r06d), now on purpose.  A/B on one box (profiles/r06f, B = 8, steps/s):
-// 0 nothing 84.9-85.9k; 1 the barrier alone 92.4-93.0k; 2 an s_memrealtime read instead 92.9-
-// 93.6k; 3 barrier + s_sleep 1 96.5-99.0k (the product form); 4 the stamp's clock arithmetic kept in a
-// register 97.1-98.1k; the round-5 mark itself 96.7-98.1k.  tests/test_sampler_codegen.py pins
-// the sleep behind every publish.
-#ifndef SL_PUBFENCE
-#define SL_PUBFENCE 3
-#endif
-// The pause, in s_sleep units of 64 cycles.  Swept on one box (profiles/r06s, r06t, B = 8,
-// steps/s): 1 96.3-98.6k, 2 100.6-101.8k, 3 101.8-104.5k, 4 104.1-104.7k, 6 102.1-103.0k,
-// 8 99.7-100.3k, 12 94.8-95.2k; a sleep between re-polls of a missing granule instead
-// (LDM_GRAN_SLEEP 1) 90-94k.
-// Double-buffered activation stage (SL_XSDB 1): layer L stages into xs[L & 1] and its abort
-// flag is slot L % 3, so the workgroup barrier BEFORE a layer's granule polls (the WAR guard on
-// the single xs buffer, and the flag reset) goes.  WAR on xs[L & 1]: its last reads were layer
-// L - 2's rows, and every wave finishes those before it arrives at layer L - 1's post-poll
-// barrier, which every writer of layer L has passed.  Flag slot (L + 1) % 3 is reset during
-// layer L by thread 0: its last readers (layer L - 2, right after their post-poll barrier)
-// passed layer L - 1's barrier before thread 0 could get here, and any layer-(L + 1) failure
-// write comes after layer L's barrier, which thread 0 reaches only after the reset.
-#ifndef SL_XSDB
-#define SL_XSDB 0
-#endif
-#ifndef SL_POLLW
-#define SL_POLLW 8
-#endif
-#ifndef SL_PUBSLEEP
-#define SL_PUBSLEEP 4
-#endif
+// in issue order (a scheduling barrier), and the wave sleeps kPubSleep intervals of 64 cycles
+// before it starts polling -- fewer polls hit the lines the other producers are still writing.
+// 4 is the top of the sweep (profiles/r06s, r06t: 104.1-104.7k steps/s at B = 8 against 96.3-
+// 98.6k at 1 and 99.7-100.3k at 8; the barrier + sleep form against the others: profiles/r06f).
+// tests/test_sampler_codegen.py pins the sleep behind every publish.
+constexpr int kPubSleep = 4;
 __device__ __forceinline__ void after_publish() {
-    if (SL_PUBFENCE == 1) __builtin_amdgcn_sched_barrier(0);
-    if (SL_PUBFENCE == 2) {
-        const uint64_t t = __builtin_amdgcn_s_memrealtime();
-        asm volatile("" ::"s"(t));
-    }
-    if (SL_PUBFENCE == 3) {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_sleep(SL_PUBSLEEP);
-    }
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_sleep(kPubSleep);
 }
-// SL_PUBFENCE 4: the round-5 stamp's mark 4 alone, kept in a register (no global stamp buffer):
-// the elapsed time since the previous publish accumulated per wave, consumed at the end
-struct PubClock {
-    uint64_t t = 0, acc = 0;
-    __device__ __forceinline__ void start() {
-        if (SL_PUBFENCE == 4) t = __builtin_amdgcn_s_memrealtime();
-    }
-    __device__ __forceinline__ void mark() {
-        if (SL_PUBFENCE == 4) {
-            const uint64_t now = __builtin_amdgcn_s_memrealtime();
-            acc += now - t;
-            t = now;
-        }
-    }
-    __device__ __forceinline__ void end() {
-        if (SL_PUBFENCE == 4) asm volatile("" ::"s"(acc));
-    }
-};
-// SL_MARKS (A/B builds only): a bit mask of the marks to keep without the rest of the stamps
-#ifndef SL_MARKS
-#define SL_MARKS 0
-#endif
-#define SL_ANY (SL_STAMP || SL_MARKS)
-#ifndef SL_PRIO
-#define SL_PRIO 0
-#endif
-#ifndef SL_NAPS
-#define SL_NAPS 0
-#endif
-#if SL_ANY
+#if SL_STAMP
 __device__ unsigned long long g_sl_stamp[256][kRepWaves][8];
 #endif
 struct SlStamp {
     uint64_t acc[6] = {0, 0, 0, 0, 0, 0};
     uint64_t t = 0;
     __device__ __forceinline__ void start() {
-        if (SL_ANY) t = __builtin_amdgcn_s_memrealtime();
+        if (SL_STAMP) t = __builtin_amdgcn_s_memrealtime();
     }
     __device__ __forceinline__ void mark(int k) {
-        if ((SL_NAPS >> k) & 1) __builtin_amdgcn_s_sleep(1);
-        if (SL_STAMP || ((SL_MARKS >> k) & 1)) {
+        if (SL_STAMP) {
             const uint64_t now = __builtin_amdgcn_s_memrealtime();
             acc[k] += now - t;
             t = now;
         }
     }
     __device__ __forceinline__ void flush(int wave) {
-#if SL_ANY
+#if SL_STAMP
         if ((threadIdx.x & 63) == 0 && blockIdx.x < 256)
             for (int i = 0; i < 6; ++i) g_sl_stamp[blockIdx.x][wave][i] = acc[i];
 #endif
@@ -660,15 +580,14 @@ __global__ __launch_bounds__(64 * kRepWaves) void sample_replica_kernel(LoopArgs
     constexpr int NV = R * MBX, LB = NV >= 16 ? 4 : NV >= 8 ? 3 : NV >= 4 ? 2 : 1;
     constexpr int NT = 64 * NWV;
     static_assert(RO * MBX <= NV, "out-projection values fit the reduce-scatter");
-    // LDS: [4] flags | xs [1 + SL_XSDB][MBX][H] | in-proj weights [8 waves][R][NJD][64 lanes] u32x4 |
-    //      out-proj weights [8 waves][RO][NJH][64] u32x4 | the last SL_LDSBLK blocks' weights
-    //      [SL_LDSBLK][8 waves][R][NJH][64] u32x4.  The other residual blocks' weights (32 VGPRs
+    // LDS: [4] flags | xs [MBX][H] | in-proj weights [8 waves][R][NJD][64 lanes] u32x4 |
+    //      out-proj weights [8 waves][RO][NJH][64] u32x4 | the last kLdsBlocks blocks' weights
+    //      [kLdsBlocks][8 waves][R][NJH][64] u32x4.  The other residual blocks' weights (32 VGPRs
     //      of bf16 pairs each) live in registers.
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int* ok = reinterpret_cast<int*>(smem);
-    float* const xsb = smem + 4;                         // [1 + SL_XSDB][MBX][H]
-    float* xs = xsb;
-    u32x4* lwi = reinterpret_cast<u32x4*>(smem + 4 + (1 + SL_XSDB) * MBX * H);
+    float* xs = smem + 4;                                // [MBX][H]
+    u32x4* lwi = reinterpret_cast<u32x4*>(smem + 4 + MBX * H);
     u32x4* lwo = lwi + NWV * R * NJD * 64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned* sync = a.ctr;
@@ -685,8 +604,10 @@ __global__ __launch_bounds__(64 * kRepWaves) void sample_replica_kernel(LoopArgs
     __syncthreads();
     if (!*ok) return;
     const unsigned xcc = s_xcc, nloc = s_nloc;
-    // every wave has read ok[0] above; the slots are set before the first layer's barrier
-    // (the step-0 in-projection stage's)
+    // every wave has read ok[0] above; it is set again before the first layer's barrier (the
+    // step-0 in-projection stage's).  Only ok[0] is used; the store stays three words wide
+    // because narrowing it changes the kernel's register allocation (the weight-load address
+    // registers permute), and this file's device code is pinned to the measured build.
     if (threadIdx.x == 0) ok[0] = ok[1] = ok[2] = 1;
     const int B = a.B, D = D_;
     const int nsh = (B > (int)xcc) + (B > (int)xcc + 8);     // shapes of this replica
@@ -694,8 +615,8 @@ __global__ __launch_bounds__(64 * kRepWaves) void sample_replica_kernel(LoopArgs
     const int gw = (int)s_rank * NWV + wave;                  // 0 .. 32 NWV - 1
     const int row0 = gw * R, orow0 = gw * RO;
 
-    constexpr int NBR = NB - SL_LDSBLK;                  // blocks with register weights
-    static_assert(NBR >= 1 && NBR <= NB, "SL_LDSBLK in 0..3");
+    constexpr int NBR = NB - kLdsBlocks;                 // blocks with register weights
+    static_assert(NBR >= 1 && NBR <= NB, "kLdsBlocks in 0..3");
     u32x4 wb[NBR][R][NJH];
 #pragma unroll
     for (int k = 0; k < NBR; ++k) load_rows_bf16<R, NJH>(wb[k], a.w_blk[k], row0, 2 * H, H, lane);
@@ -748,19 +669,8 @@ __global__ __launch_bounds__(64 * kRepWaves) void sample_replica_kernel(LoopArgs
         if (tagged) return true;
         return replica_sync(sync, xcc, nloc, phase, ok, a.spin_limit);
     };
-    // stage this replica's [MBX][K] activations of the layer that published under tag `tg`
     SlStamp stp;
-    // each staged layer's buffer and abort-flag slot (SL_XSDB), in the order every wave stages
-    int lyr = 0;
-    int* okc = ok;
-    auto begin_layer = [&]() {
-        if (SL_XSDB) {
-            xs = xsb + (size_t)(lyr & 1) * MBX * H;
-            okc = ok + lyr % 3;
-            if (threadIdx.x == 0) ok[(lyr + 1) % 3] = 1;
-        }
-        ++lyr;
-    };
+    // stage this replica's [MBX][K] activations of the layer that published under tag `tg`
     auto stage_act = [&](float* dst, const float* plain, const u64* gran, int K, unsigned tg) {
         if (!tagged || gran == nullptr) {
 #pragma unroll
@@ -768,36 +678,21 @@ __global__ __launch_bounds__(64 * kRepWaves) void sample_replica_kernel(LoopArgs
             __syncthreads();
             return true;
         }
-        if (!SL_XSDB) {
-            if (threadIdx.x == 0) *okc = 1;
-            __syncthreads();
-        }
+        // the WAR guard on the single xs buffer, and the flag reset.  The barrier also keeps
+        // the polls late: a double-buffered stage without it ran 68k steps/s against 104k
+        // (profiles/r06w)
+        if (threadIdx.x == 0) *ok = 1;
+        __syncthreads();
         // only this replica's nsh shapes are published (rows of a missing second shape are
-        // computed on whatever the LDS holds and never written)
-#if SL_PRIO
-        __builtin_amdgcn_s_setprio(0);           // (A/B) polling waves yield issue to computing ones
-#endif
-        // (SL_POLLW < 8, A/B builds: only the first SL_POLLW waves poll, more granules each)
-        bool good = true;
-        if constexpr (SL_POLLW >= kRepWaves) {
-            good = stage_tagged<NT, 2>(dst, gran, nsh * K, tg, status, a.spin_limit);
-        } else {
-            if (wave < SL_POLLW)
-                good = stage_tagged<64 * SL_POLLW, 2 * kRepWaves / SL_POLLW>(
-                    dst, gran, nsh * K, tg, status, a.spin_limit);
-        }
-#if SL_PRIO
-        __builtin_amdgcn_s_setprio(SL_PRIO);
-#endif
+        // computed on whatever the LDS holds and never written); every wave polls
+        const bool good = stage_tagged<NT, 2>(dst, gran, nsh * K, tg, status, a.spin_limit);
         stp.mark(0);
-        if (!good) *okc = 0;
+        if (!good) *ok = 0;
         __syncthreads();
         stp.mark(1);
-        return *okc != 0;
+        return *ok != 0;
     };
     stp.start();
-    PubClock pclk;
-    pclk.start();
 
     for (int s = 0; s < a.steps; ++s) {
         const int t = a.t_hi - s;
@@ -814,7 +709,6 @@ __global__ __launch_bounds__(64 * kRepWaves) void sample_replica_kernel(LoopArgs
         const float c1 = a.c1[t], c2 = a.c2[t], sg = a.sg[t];
         // in-projection over this replica's shapes (step 0: the caller's x; later: the
         // previous out-projection's tagged granules)
-        begin_layer();
         if (tagged && s > 0) {
             if (!stage_act(xs, nullptr, xgr + (size_t)(s & 1) * MBX * D, D, phase)) return;
         } else {
@@ -835,7 +729,6 @@ __global__ __launch_bounds__(64 * kRepWaves) void sample_replica_kernel(LoopArgs
                 else publish(hrep + (size_t)qb * H + mh, acc + bi);
             }
             after_publish();
-            pclk.mark();
             stp.mark(4);
             if (SL_STAMP) stp.acc[5] += 1;
         }
@@ -848,8 +741,7 @@ __global__ __launch_bounds__(64 * kRepWaves) void sample_replica_kernel(LoopArgs
             if (!alive) return;
             const float* hin = hrep + (size_t)(k & 1) * MBX * H;
             float* hout = hrep + (size_t)((k + 1) & 1) * MBX * H;
-            begin_layer();
-            if (!stage_act(xs, hin, tagged ? hgr + (size_t)(k & 1) * MBX * H : nullptr, H,
+                if (!stage_act(xs, hin, tagged ? hgr + (size_t)(k & 1) * MBX * H : nullptr, H,
                            phase)) {
                 alive = false;
                 return;
@@ -873,7 +765,6 @@ __global__ __launch_bounds__(64 * kRepWaves) void sample_replica_kernel(LoopArgs
                 else publish(hout + (size_t)qb * H + mh, hv);
             }
             after_publish();
-            pclk.mark();
             stp.mark(4);
             if (SL_STAMP) stp.acc[5] += 1;
             alive = boundary();
@@ -884,7 +775,6 @@ __global__ __launch_bounds__(64 * kRepWaves) void sample_replica_kernel(LoopArgs
         block(std::integral_constant<int, 2>{});
         block(std::integral_constant<int, 3>{});
         if (!alive) return;
-        begin_layer();
         if (!stage_act(xs, hrep + (size_t)(NB & 1) * MBX * H,
                        tagged ? hgr + (size_t)(NB & 1) * MBX * H : nullptr, H, phase))
             return;
@@ -906,14 +796,12 @@ __global__ __launch_bounds__(64 * kRepWaves) void sample_replica_kernel(LoopArgs
                                    xv, phase);
             }
             after_publish();
-            pclk.mark();
             stp.mark(4);
             if (SL_STAMP) stp.acc[5] += 1;
         }
         if (!boundary()) return;
     }
     stp.flush(wave);
-    pclk.end();
 }
 
 // Residency: every workgroup of the grid must be resident at once (the grid barriers wait for
@@ -965,8 +853,8 @@ int cur_dev() {
 size_t replica_lds(int D, int MBX) {
     const int H = 1024, W = kRepWaves, R = H / (32 * W), RO = D / (32 * W);
     const int NJD = (D + 511) / 512, NJH = 2;
-    return 16 + (size_t)(1 + SL_XSDB) * MBX * H * 4 +
-           (size_t)W * (R * NJD + RO * NJH + SL_LDSBLK * R * NJH) * 64 * 16;
+    return 16 + (size_t)MBX * H * 4 +
+           (size_t)W * (R * NJD + RO * NJH + kLdsBlocks * R * NJH) * 64 * 16;
 }
 
 template <int D_, int MBX>

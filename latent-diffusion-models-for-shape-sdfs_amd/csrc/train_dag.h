@@ -1,4 +1,4 @@
-// The persistent training-step kernel's job table (host builder: denoiser_train.hip
+// The persistent training-step kernel's job table (host builder: train_dag_build.hip
 // build_dag; device: train_dag.hip).  Internal, not part of the ABI.
 //
 // One DDPM training step (config 2: q_sample -> denoiser forward -> eps-MSE -> backward ->

@@ -1,5 +1,5 @@
 // The whole DDPM training step (config 2, SURVEY.md §8(a) A6/A7/A9 + AdamW) as ONE persistent
-// launch: train_dag_kernel walks the job DAG that denoiser_train.hip build_dag records from the
+// launch: train_dag_kernel walks the job DAG that train_dag_build.hip build_dag records from the
 // launch-per-GEMM step (train_dag.h).  Why: the launch-per-GEMM step spends two thirds of its
 // time in per-launch fixed cost -- argument issue, ring fill, the epilogue tail of the last
 // workgroups, the gap to the next launch -- and its AdamW (HBM-bound) starts only after the
@@ -32,12 +32,6 @@
 
 #include <mutex>
 
-// DAG_EPI_WT 0 (timing-only A/B builds, results WRONG): the GEMM jobs' epilogue stores plain
-// instead of write-through -- what the plain-store hand-off lever could gain at
-// most, before any same-XCD / cross-XCD split of the stores
-#ifndef DAG_EPI_WT
-#define DAG_EPI_WT 1
-#endif
 namespace ldm {
 namespace dag {
 namespace {
@@ -60,11 +54,9 @@ typedef const __attribute__((address_space(4))) ldm_gemm_prob_t KProb;
 // path's 8-wave tile at ~47 and 12 waves per CU at ~70 (profiles/r05n): the per-CU operand
 // stream scales with the waves issuing it, and fence-free hand-offs need one workgroup per CU.
 constexpr int NW = kThreads / 64, kWgPerCu = 1;
-// LDS per workgroup (the ring): 128 KiB; DAG_LDS_KB=160 (A/B builds) deepens every ring
-#ifndef DAG_LDS_KB
-#define DAG_LDS_KB 128
-#endif
-constexpr int kLdsBytes = DAG_LDS_KB * 1024;
+// LDS per workgroup (the ring).  128 KiB: deeper rings (159 KiB) measured no faster, 2945
+// steps/s against 2959-2963 (profiles/r05y)
+constexpr int kLdsBytes = 128 * 1024;
 template <int CFG>
 struct TileCfg {
     static constexpr int BM = CFG == TILE_W ? 128 : 64;
@@ -306,7 +298,8 @@ __device__ __forceinline__ void gemm_job(KNode& N, int job, const float* eps,
 #pragma unroll
         for (int bb = 1; bb < RM * RN; ++bb)
             if (b == bb) c = acc[bb / RN][bb % RN];
-        epi_lds_block<BM, DAG_EPI_WT != 0>(smem, 0, wl, lane, wr, h, r32, L, c, i, nb, e);
+        // write-through stores: the next job's loads of these bytes are the hand-off
+        epi_lds_block<BM, true>(smem, 0, wl, lane, wr, h, r32, L, c, i, nb, e);
     }
 }
 

@@ -1009,16 +1009,14 @@ int launch_fast(const ConvKArgs& ka, dim3 grid, int lds, hipStream_t s) {
     return launch_status("ldm_conv1d");
 }
 
-// register weights (conv1d_fast_kernel MAXC) when every wave's chunks fit kWregChunks
-// (UNET_WREG 0: the LDS-staged weights, the round-5 form)
-#ifndef UNET_WREG
-#define UNET_WREG 1
-#endif
+// register weights (conv1d_fast_kernel MAXC) when every wave's chunks fit kWregChunks: every
+// conv of the UNet.  12.15k -> 12.30k steps/s at B = 1 against the LDS-staged weights
+// (profiles/r06aa)
 constexpr int kWregChunks = 8;
 
 template <typename TW, int TP, int NS>
 int launch_fast_nbw(const ConvKArgs& ka, dim3 grid, int lds, hipStream_t s) {
-    if (UNET_WREG && ka.pl.nchunks <= 4 * kWregChunks && dev_knob("LDM_CONV_WREG", 1))
+    if (ka.pl.nchunks <= 4 * kWregChunks && dev_knob("LDM_CONV_WREG", 1))
         return launch_fast<TW, TP, NS, 1, kWregChunks>(ka, grid, lds, s);
     int nw = 0;
     for (int i = 0; i < NS; ++i) nw = ka.pl.s[i].nw > nw ? ka.pl.s[i].nw : nw;

@@ -701,7 +701,7 @@ TRAIN_FORMS = {"auto": 0, "launches": 1, "dag": 2}
 
 def train_step_config(form: str = "auto", spin_limit: int = 0) -> None:
     """Form of ``denoiser_train_step_adamw`` on the current device (``ldm_train_step_config``):
-    "auto" (the form measured faster for the configuration: denoiser_train.hip ``dag_auto``),
+    "auto" (the form measured faster for the configuration: train_dag_build.hip ``dag_auto``),
     "launches" (one launch per GEMM group + AdamW), "dag" (the one-launch step, required).  Same
     bits either way.  ``spin_limit``: MICROSECONDS (s_memrealtime time) one DAG dependency wait
     may take before the launch gives up (0 = the default, 2 s; 1 us makes waits give up at once

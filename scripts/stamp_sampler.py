@@ -1,8 +1,10 @@
 """Per-phase times of the XCD-replica sampling loop (csrc/sample_loop.hip
-sample_replica_kernel), from its stamps (on in the product build since round 5, SL_STAMP = 1):
-every wave sums the s_memrealtime ticks (100 MHz) of each phase of every layer it runs -- own
-granules landed, the workgroup's staging barrier, row dot products, reduce-scatter, epilogue +
-publish.  Usage: python scripts/stamp_sampler.py [B]"""
+sample_replica_kernel), from its stamps: every wave sums the s_memrealtime ticks (100 MHz) of
+each phase of every layer it runs -- own granules landed, the workgroup's staging barrier, row
+dot products, reduce-scatter, epilogue + publish.  The stamps are off in the product build (no
+stamp code, no ldm_dev_sample_stamps export); they need a diagnostic library built with
+-DSL_STAMP=1 (the build line of scripts/trace_dag.py).
+Usage: LDM_SDF_LIB=<...>/libldm_diag.so python scripts/stamp_sampler.py [B]"""
 import ctypes as C
 import os
 import sys

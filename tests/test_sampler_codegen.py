@@ -5,9 +5,9 @@ Round 5's fast sampler depended on a build accident: the loop's weights overflow
 VGPRs a wave has at two waves per SIMD, the compiler spilled residual-block weight vectors to
 scratch and reloaded them SERIALLY every step (scratch_load + s_waitcnt vmcnt(0), 5-6 times),
 and the diagnostic stamps merely changed which values spilled.  Round 6 keeps the last residual
-block's weights in LDS (SL_LDSBLK), which leaves the kernel without any scratch; and what the
+block's weights in LDS (kLdsBlocks), which leaves the kernel without any scratch; and what the
 stamps really bought -- the wave pausing right after a layer's publish before it polls for the
-next layer -- is now built on purpose (SL_PUBFENCE: a scheduling barrier + s_sleep SL_PUBSLEEP,
+next layer -- is now built on purpose (after_publish(): a scheduling barrier + s_sleep kPubSleep,
 4 after the round-6 sweep).  This test fails if a change (or a compiler update) brings the
 spills back to the bench's configuration (D = 256, B <= 8: sample_replica_kernel<256, 1>), with
 or without the stamps, or separates a publish from its pause."""
