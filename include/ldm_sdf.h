@@ -143,7 +143,8 @@ int ldm_grid_coords(int N, int k0, int k1, float vs, float origin, float* xyz_ou
 int ldm_decoder_fold(const ldm_decoder_t* w, const float* z, int B, float* beta_out,
                      ldm_stream_t s);
 /* out[0] (device) = max over shapes b of sqrt(mean_l z[b][l]^2), z fp32 [B][L]: the latent
- * scale the Python decode's dtype="auto" picks its 16-bit format by. */
+ * scale the Python decode's dtype="auto" picks its 16-bit format by.
+ * Non-finite input propagates: any NaN element gives NaN, else any +-Inf element gives +Inf. */
 int ldm_latent_rms_max(const float* z, int B, int L, float* out, ldm_stream_t s);
 /* A1+A3 grid mode: out fp32 [B][(k1-k0)*N*N] (the z-slab [k0,k1) of each shape's N^3 grid). */
 int ldm_decoder_grid_fwd(const ldm_decoder_t* w, const float* beta, int B, int N, int k0,

@@ -35,6 +35,11 @@ __global__ void grid_coords_kernel(int N, int k0, int npts, float vs, float orig
 
 // ------------------------------------------------------------------------------------------
 // A2: beta[b][l][f] = sum_k wz[l][f][k] z[b][k] + bz[l][f]   (l = 0: layer 0, 1: layer 4)
+// Summed in fp64 (the fp32 products are exact there) and rounded to fp32 once.  An fp32 fmaf
+// chain over L = 1024 left beta a few fp32 ulps off (median 2e-7, max 4e-6 at |beta| ~ 1), more
+// than the fp16 kernel's hi + lo pair resolves (~22 bits): that noise flipped 16-bit activation
+// roundings and put the widen-skip fp16 decode a median 3.3e-5 from the 16-bit oracle, which
+// folds exactly, instead of 1.6e-7.  B * 2 * H chains of L: microseconds.
 // ------------------------------------------------------------------------------------------
 __global__ void fold_kernel(const float* __restrict__ wz, const float* __restrict__ bz,
                             const float* __restrict__ z, int B, int L, int H,
@@ -46,9 +51,9 @@ __global__ void fold_kernel(const float* __restrict__ wz, const float* __restric
     const int b = id / (2 * H);
     const float* w = wz + ((size_t)l * H + f) * L;
     const float* zz = z + (size_t)b * L;
-    float acc = 0.f;
-    for (int k = 0; k < L; ++k) acc = fmaf(w[k], zz[k], acc);
-    beta[id] = acc + bz[l * H + f];
+    double acc = 0.0;
+    for (int k = 0; k < L; ++k) acc = fma((double)w[k], (double)zz[k], acc);
+    beta[id] = (float)(acc + (double)bz[l * H + f]);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -58,7 +63,14 @@ __global__ void fold_kernel(const float* __restrict__ wz, const float* __restric
 // through LDS.  Here rather than as torch reductions: the process's first torch pow / mean /
 // sqrt / max on the GPU loads their code objects (~0.25 s on a fresh process, DESIGN.md §7 round
 // 6), while this kernel sits in the code object the decode itself loads.
+// The max propagates NaN (fmaxf would drop it and let a batch with a NaN latent pick a 16-bit
+// format on the device while the host decision picks fp32): a NaN element gives NaN, an Inf
+// element +Inf, NaN wins over Inf.
 // ------------------------------------------------------------------------------------------
+__device__ __forceinline__ float max_keep_nan(float a, float b) {
+    return (a > b || a != a) ? a : b;      // a if it is NaN or larger; else b, NaN included
+}
+
 __global__ __launch_bounds__(256) void rms_max_kernel(const float* __restrict__ z, int B, int L,
                                                       float* __restrict__ out) {
     __shared__ float wmax[4];
@@ -70,11 +82,12 @@ __global__ __launch_bounds__(256) void rms_max_kernel(const float* __restrict__ 
         for (int k = lane; k < L; k += 64) s = fmaf(zz[k], zz[k], s);
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-        m = fmaxf(m, sqrtf(s / (float)L));
+        m = max_keep_nan(m, sqrtf(s / (float)L));
     }
     if (lane == 0) wmax[wave] = m;
     __syncthreads();
-    if (threadIdx.x == 0) out[0] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    if (threadIdx.x == 0)
+        out[0] = max_keep_nan(max_keep_nan(wmax[0], wmax[1]), max_keep_nan(wmax[2], wmax[3]));
 }
 
 // ------------------------------------------------------------------------------------------

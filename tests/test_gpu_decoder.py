@@ -199,6 +199,162 @@ def test_split_vs_lowp_oracle(dev, decoder, dtype, scale):
         assert e_lo <= bound, (lay, e_lo)
 
 
+@pytest.fixture(scope="module")
+def widen_decoder():
+    from ldm_sdf import SDFDecoder
+    from tests.test_decode_contract import decoder_params
+    p = decoder_params("widen")
+    return SDFDecoder(1024, weights=p.weights, biases=p.biases)
+
+
+@pytest.fixture(scope="module")
+def decoders(decoder, widen_decoder):
+    return {"deepsdf": decoder, "widen": widen_decoder}
+
+
+# --------------------------------------------------------------------------------------------
+# dtype="auto" at its thresholds: the pick, and SURVEY §8(c)'s bound for the dtype picked, on the
+# calibration set of tests/test_decode_contract.py (whose CPU half holds the 16-bit oracle to the
+# same bounds).  Latents are normalised to T * (1 - 1e-3): the device RMS is within fp32 rounding
+# of the target, so this is the largest scale at which the pick is certain.
+# --------------------------------------------------------------------------------------------
+def _auto_threshold(dtype):
+    from ldm_sdf import api
+    return {"bf16": api.BF16_MAX_LATENT_RMS, "fp16": api.FP16_MAX_LATENT_RMS}[dtype]
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("name", ["deepsdf", "widen"])
+def test_auto_contract_at_threshold_points(dev, decoders, name, dtype):
+    """decode_points with the default dtype, latents just inside ``dtype``'s threshold: "auto"
+    picks ``dtype`` and the result is inside its bound vs the fp64 decoder; vs the 16-bit oracle
+    the median stays at fp32 noise (the form of test_split_vs_lowp_oracle)."""
+    import ldm_sdf
+    from ldm_sdf import api
+    from tests.test_decode_contract import SEEDS, calibration_case
+    r = _auto_threshold(dtype) * (1 - 1e-3)
+    worst = 0.0
+    for seed in SEEDS:
+        z, pts, want, lowp = calibration_case(name, seed, r, dtype)
+        zd = z.to(dev)
+        api.clear_auto_cache()
+        assert ldm_sdf.resolve_decode_dtype("auto", zd) == dtype
+        got = ldm_sdf.decode_points(decoders[name], zd, pts.to(dev)).cpu().double()
+        e64 = float((got - want).abs().max())
+        d_lo = (got - lowp).abs()
+        e_lo, m_lo = float(d_lo.max()), float(d_lo.median())
+        print(f"auto contract {name} {dtype} rms {r:.4f} seed {seed}: device vs fp64 max "
+              f"{e64:.3e}, vs lowp max {e_lo:.3e} median {m_lo:.2e}")
+        assert m_lo <= 2e-5, (name, dtype, seed, m_lo)
+        worst = max(worst, e64)
+    print(f"auto contract {name} {dtype} rms {r:.4f}: device vs fp64 max over seeds "
+          f"{worst:.3e} (bound {TOL[dtype]:.0e})")
+    assert worst <= TOL[dtype], (name, dtype, worst)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("name", ["deepsdf", "widen"])
+def test_auto_contract_at_threshold_grid(dev, decoders, name, dtype):
+    """The same through decode(): a 17^3 grid (4913 points per shape, a ragged last tile),
+    seed 100's latents, vs the fp64 decoder on the oracle's grid coordinates."""
+    import ldm_sdf
+    from ldm_sdf import api
+    from oracle import ref_cpu as R
+    from tests.test_decode_contract import calibration_inputs, decoder_params
+    p = decoder_params(name)
+    z, _ = calibration_inputs(100, p.latent_dim, _auto_threshold(dtype) * (1 - 1e-3))
+    zd = z.to(dev)
+    api.clear_auto_cache()
+    assert ldm_sdf.resolve_decode_dtype("auto", zd) == dtype
+    got = ldm_sdf.decode(decoders[name], zd, 17).cpu().double().reshape(4, -1)
+    with torch.inference_mode():
+        want = R.decoder_forward(p, z.double(), torch.from_numpy(R.grid_coords_np(17)).double())
+    err = float((got - want).abs().max())
+    print(f"auto contract grid 17^3 {name} {dtype}: device vs fp64 max {err:.3e}")
+    assert err <= TOL[dtype], (name, dtype, err)
+
+
+# --------------------------------------------------------------------------------------------
+# Slot independence, bitwise: the value at a point depends on the point and its shape's latent
+# only -- not on its tile, 32-point chunk or lane, not on its shape's position in the batch, and
+# not on whether the kernel formed the coordinates or read them.
+# --------------------------------------------------------------------------------------------
+SLOT_CASES = [("deepsdf", "fp32"), ("deepsdf", "bf16"), ("deepsdf", "fp16"),
+              ("widen", "fp16"), ("widen", "bf16")]
+
+
+def _slot_inputs(B, P, L, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(B, L, generator=g) * 0.1, torch.rand(B, P, 3, generator=g) * 2 - 1, g
+
+
+@pytest.mark.parametrize("name,dtype", SLOT_CASES)
+def test_point_permutation_bitwise(dev, decoders, name, dtype):
+    """A random permutation of 1000 points moves every point to another tile, chunk and lane
+    (the MFMA B-operand column and the lane that stores the result): same bits."""
+    import ldm_sdf
+    dec = decoders[name]
+    z, pts, g = _slot_inputs(3, 1000, dec.latent_dim, 41)
+    perm = torch.randperm(1000, generator=g)
+    assert int((perm % 32 != torch.arange(1000) % 32).sum()) > 900
+    zd, pd = z.to(dev), pts.to(dev)
+    base = ldm_sdf.decode_points(dec, zd, pd, dtype=dtype)
+    moved = ldm_sdf.decode_points(dec, zd, pd[:, perm.to(dev)].contiguous(), dtype=dtype)
+    assert torch.equal(moved, base[:, perm.to(dev)])
+
+
+@pytest.mark.parametrize("name,dtype", SLOT_CASES)
+def test_shape_permutation_bitwise(dev, decoders, name, dtype):
+    """Shapes permuted with no fixed point (3 tiles per shape, the last ragged): every shape gets
+    another per-shape aux slot and other tile indices; same bits."""
+    import ldm_sdf
+    dec = decoders[name]
+    z, pts, _ = _slot_inputs(5, 300, dec.latent_dim, 43)
+    pb = torch.tensor([2, 0, 4, 1, 3])
+    assert bool((pb != torch.arange(5)).all())
+    zd, pd = z.to(dev), pts.to(dev)
+    base = ldm_sdf.decode_points(dec, zd, pd, dtype=dtype)
+    moved = ldm_sdf.decode_points(dec, zd[pb.to(dev)].contiguous(),
+                                  pd[pb.to(dev)].contiguous(), dtype=dtype)
+    assert torch.equal(moved, base[pb.to(dev)])
+
+
+@pytest.mark.parametrize("N,k0,k1", [(33, 0, 33), (40, 13, 27), (257, 255, 257)])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
+def test_grid_mode_equals_points_mode_bitwise(dev, decoder, dtype, N, k0, k1):
+    """Coordinates formed in the kernel (grid mode) against the same coordinates read from
+    memory (points mode, the mode pinned tightly against the 16-bit oracle): a one-voxel slip
+    at a fine resolution sits far below the fp64 bounds but not below this.  33^3 x 2 shapes is
+    1124 tiles: the persistent loop, the ragged tail and a shape boundary inside a workgroup's
+    walk; (257, 255, 257) is a fine grid's last two slabs."""
+    from ldm_sdf import ops
+    g = torch.Generator().manual_seed(47)
+    z = (torch.randn(2, 256, generator=g) * 0.1).to(dev)
+    desc = decoder.device_pack(dtype, dev)["desc"]
+    beta = ops.decoder_fold(desc, z)
+    xyz = ops.grid_coords(N, k0, k1, device=dev)[None].expand(2, -1, -1).contiguous()
+    grid = ops.decoder_grid_fwd(desc, beta, N, k0, k1)
+    pts = ops.decoder_points_fwd(desc, beta, xyz)
+    assert grid.shape == (2, k1 - k0, N, N)
+    assert torch.equal(grid.reshape(2, -1), pts)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
+def test_decode_bbox_equals_points_bitwise(dev, decoder, dtype):
+    """A non-default box reaches the kernel's coordinates (voxel size and origin) as it reaches
+    ``grid_coords``."""
+    import ldm_sdf
+    from ldm_sdf import ops
+    g = torch.Generator().manual_seed(53)
+    z = (torch.randn(2, 256, generator=g) * 0.1).to(dev)
+    bbox = (-0.5, 1.5)
+    xyz = ops.grid_coords(33, bbox=bbox, device=dev)
+    assert float(xyz.min()) == -0.5 and abs(float(xyz.max()) - 1.5) < 1e-6
+    vol = ldm_sdf.decode(decoder, z, 33, bbox=bbox, dtype=dtype)
+    pts = ldm_sdf.decode_points(decoder, z, xyz, dtype=dtype)
+    assert torch.equal(vol.reshape(2, -1), pts)
+
+
 def test_removed_layouts_fail_loudly(dev, decoder):
     """pass8 / quarter (ABI 5) and split16 (ABI 7) descriptors get LDM_ENOSYS, not a kernel."""
     from ldm_sdf import _capi as capi, ops
