@@ -42,11 +42,13 @@ using namespace dec;
 
 // k-steps of A fragments in flight per wave (register ring depth = one 4-step stream group)
 constexpr int kFsD = 4;
-// FV (kernel variant, template): bit 0 = an in-stream barrier sits after the step's SECOND
-// MFMA pair instead of its first; bit 1 = one LDS base per 4-step group (dev-build A/B:
-// LDM_FS_V=<FV>).  Measured and dropped: layers 2..7 as one runtime loop with every part kind
-// inlined once (74 -> 50 KB of code, 1.2 % slower: profiles/r04b/ab_decoder_v.log).
-constexpr int kFsDefaultV = 2;   // group base: +0.5 % (profiles/r04b/ab_decoder_v.log)
+// History: a kernel-variant template parameter carried two switches until it was frozen
+// (DESIGN.md §5 "Retired build knobs").  Bit 1, one LDS base per 4-step group instead of an
+// address per step, measured +0.5 % (profiles/r04b/ab_decoder_v.log, r04a/
+// ab_decoder_groupbase.log) and is what group4 does.  Bit 0, the in-stream barrier after the
+// step's SECOND MFMA pair instead of its first, never became the default (no log kept) and is
+// gone.  Also measured and dropped: layers 2..7 as one runtime loop with every part kind inlined
+// once (74 -> 50 KB of code, 1.2 % slower: profiles/r04b/ab_decoder_v.log).
 
 constexpr int kFsStep = 2048;                       // one wave's A fragments of one k-step
 // activation buffer: 32 positions of 4 KiB + position 32 = the tile's aux B fragments
@@ -135,7 +137,6 @@ struct FSrc {
     bool none = false;        // nothing to prefetch (the tile's last part)
 };
 
-template <int FV>
 struct FCtx {
     int lane, wave, h;
     uint32_t voff;            // lane * 16
@@ -159,8 +160,7 @@ struct FCtx {
     bool st_on;
 };
 
-template <int FV>
-__device__ __forceinline__ void stamp(FCtx<FV>& c) {
+__device__ __forceinline__ void stamp(FCtx& c) {
     if (FS_STAMP) {
         if (c.st_on && c.lane == 0 && c.st_i < 128) c.st[c.st_i] = __builtin_readcyclecounter();
         ++c.st_i;
@@ -171,8 +171,7 @@ __device__ __forceinline__ u32x4 bld(__amdgpu_buffer_rsrc_t r, uint32_t voff, ui
     return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }
 
-template <int FV>
-__device__ __forceinline__ void load_aux(FCtx<FV>& c, FSrc s) {
+__device__ __forceinline__ void load_aux(FCtx& c, FSrc s) {
     if (s.none) return;
     const __amdgpu_buffer_rsrc_t r = s.shape ? c.ra : c.rw;
     c.auxn[0] = bld(r, c.voff, s.off);
@@ -196,26 +195,22 @@ __device__ __forceinline__ int opaque_s(int v) {
 // weight ring in flight.  So every address is formed AT ITS USE from an opaque copy of voff
 // (a volatile asm is neither hoisted nor folded): one or two VALU per use, nothing long-lived
 // but voff itself.
-template <int FV>
-__device__ __forceinline__ char* lds_at(const FCtx<FV>& c, uint32_t off) {
+__device__ __forceinline__ char* lds_at(const FCtx& c, uint32_t off) {
     return c.smem + (opaque(c.voff) + off);
 }
 // this wave's early (0) / late (16) positions: + (2i + s) * 4 KiB + n * 1 KiB immediates
-template <int FV>
-__device__ __forceinline__ u32x4* act_w(const FCtx<FV>& c, int late) {
+__device__ __forceinline__ u32x4* act_w(const FCtx& c, int late) {
     return reinterpret_cast<u32x4*>(lds_at(c, (uint32_t)(late + 4 * c.wave) * 4096u));
 }
 // final-layer weights of (this wave, part p, m-chunk i, this lane half)
-template <int FV>
-__device__ __forceinline__ const f32x4* wl_at(const FCtx<FV>& c, int p, int i) {
+__device__ __forceinline__ const f32x4* wl_at(const FCtx& c, int p, int i) {
     const uint32_t h = opaque(c.voff) >> 9;           // lane >> 5
     return reinterpret_cast<const f32x4*>(
         c.smem + kFsAct + kFsRed + (((c.wave * 2 + p) * 2 + i) * 2) * 64 + h * 64);
 }
 
 // this lane's final partials red[wave][n][lane] (+ n * 64 floats)
-template <int FV>
-__device__ __forceinline__ float* red_w(const FCtx<FV>& c) {
+__device__ __forceinline__ float* red_w(const FCtx& c) {
     return reinterpret_cast<float*>(c.smem + kFsAct + c.wave * 4 * 64 * 4 + (opaque(c.voff) >> 2));
 }
 
@@ -232,8 +227,7 @@ __device__ __forceinline__ void fs_bar() {
 // the "early" positions; u = 1: part 1, the "late" ones); after layer 3 at skip 253, k-step
 // 4w + 2i + s at position 16 + 4w + 2i + s (layer 4 reads positions 16 + j).  Step j reads
 // position pos0 + j: the addresses are immediates from one group base.
-template <int FV>
-__device__ __forceinline__ void read_b(FCtx<FV>& c, int pos) {
+__device__ __forceinline__ void read_b(FCtx& c, int pos) {
     const u32x4* p = reinterpret_cast<const u32x4*>(lds_at(c, pos * 4096));
 #pragma unroll
     for (int n = 0; n < 4; ++n) c.b[n] = p[n * 64];
@@ -242,8 +236,7 @@ __device__ __forceinline__ void read_b(FCtx<FV>& c, int pos) {
 // Stream step r (0..3) of the 4-step stream group at c.s_iss into ring slot r: the
 // (r & 1) * 2 KiB + fragment offset folds into the load's immediate, the (r >> 1) * 4 KiB into
 // the scalar offset, so a group costs one wrap test instead of one per step.
-template <int FV>
-__device__ __forceinline__ void issue(FCtx<FV>& c, int r) {
+__device__ __forceinline__ void issue(FCtx& c, int r) {
     const uint32_t so = c.s_iss + (uint32_t)(r >> 1) * 2u * kFsStep;
     const uint32_t vo = c.voff + (uint32_t)(r & 1) * kFsStep;
     if (FS_ABL & 1) return;
@@ -251,8 +244,7 @@ __device__ __forceinline__ void issue(FCtx<FV>& c, int r) {
     c.ring[r][1] = bld(c.rw, vo + 1024u, so);
 }
 
-template <int FV>
-__device__ __forceinline__ void next_group(FCtx<FV>& c) {
+__device__ __forceinline__ void next_group(FCtx& c) {
     c.s_iss += 4u * kFsStep;
     if (c.s_iss == c.s_end) c.s_iss = c.s_beg;
 }
@@ -266,8 +258,8 @@ __device__ __forceinline__ float relu_f(float x) {
 
 // One epilogue unit u = 2t + s of the other accumulator set: HALF of tile t = 4i + n (its
 // accumulator registers 8s..8s+7 = the B fragment of k-step 2i + s).
-template <typename T, int EK, int FV>
-__device__ __forceinline__ void epi_unit(FCtx<FV>& c, const f32x16 (&accY)[2][4], int u) {
+template <typename T, int EK>
+__device__ __forceinline__ void epi_unit(FCtx& c, const f32x16 (&accY)[2][4], int u) {
     const int t = u >> 1, s = u & 1;
     const int i = t >> 2, n = t & 3;
     if (FS_ABL & 2) return;
@@ -294,8 +286,8 @@ __device__ __forceinline__ void epi_unit(FCtx<FV>& c, const f32x16 (&accY)[2][4]
 // The 16 units of an epilogue window of 16 steps k = 0..15: unit k in step k < 14, units 14
 // and 15 in step 14, none in step 15 -- so the window's LDS writes are all issued before the
 // barrier that closes it (inside step 15, see group4).
-template <typename T, int EK, int FV>
-__device__ __forceinline__ void epi_step(FCtx<FV>& c, const f32x16 (&accY)[2][4], int k) {
+template <typename T, int EK>
+__device__ __forceinline__ void epi_step(FCtx& c, const f32x16 (&accY)[2][4], int k) {
     if (EK == FE_NONE || k == 15) return;
     epi_unit<T, EK>(c, accY, k);
     if (k == 14) epi_unit<T, EK>(c, accY, 15);
@@ -312,8 +304,7 @@ __device__ __forceinline__ void epi_step(FCtx<FV>& c, const f32x16 (&accY)[2][4]
 // the final layer across waves and lane halves (lanes l and l^32 hold the same point): lanes
 // < 32 of wave w sum point chunk w's 8 partials (after the barrier that published them), add
 // the bias, tanh, store
-template <int FV>
-__device__ __forceinline__ void fin_store(const FCtx<FV>& c, int shape, int local) {
+__device__ __forceinline__ void fin_store(const FCtx& c, int shape, int local) {
     const int lane = (int)(opaque(c.voff) >> 4);     // formed here: nothing kept live (spills)
     if (local < 0 || lane >= 32) return;
     const float* rr = reinterpret_cast<const float*>(
@@ -349,21 +340,20 @@ __device__ __forceinline__ void mfma_pair(f32x16 (&acc)[2][4], const u32x4& a0, 
 // Four k-steps reading positions p0..p0+3 (ring slots 0..3), epilogue window steps K0..K0+3.
 // Rolling B fragments: chunk n of step j+1 is read as soon as step j's two MFMAs on chunk n are
 // issued (~6 MFMAs, ~190 cycles, before it is needed).  BAR = r: an LDS barrier INSIDE step r,
-// after its first (FV & 1: second) MFMA pair and before its first read of the next position:
+// after its first MFMA pair and before its first read of the next position:
 // the waves wait on each other with the step's remaining MFMAs still to issue and the next
 // position's reads still covered by them (a barrier between steps exposed one LDS round trip
 // plus the pipeline drain, ~500-750 cycles per barrier).
-template <typename T, int EK, int K0, int BAR, int FV>
-__device__ __forceinline__ void group4(FCtx<FV>& c, f32x16 (&acc)[2][4], const f32x16 (&accY)[2][4],
+template <typename T, int EK, int K0, int BAR>
+__device__ __forceinline__ void group4(FCtx& c, f32x16 (&acc)[2][4], const f32x16 (&accY)[2][4],
                                        int p0) {
-    constexpr int BP = (FV & 1) ? 2 : 1;     // MFMA pairs before the in-stream barrier
-    // FV bit 1: ONE LDS base for the group's four next positions (r * 4 KiB + n * 1 KiB fold
-    // into the ds_read immediates) instead of an address formed per step
-    const char* gbase = (FV & 2) ? lds_at(c, (p0 + 1) * 4096) : nullptr;
+    constexpr int BP = 1;                    // MFMA pairs before the in-stream barrier
+    // ONE LDS base for the group's four next positions (r * 4 KiB + n * 1 KiB fold into the
+    // ds_read immediates) instead of an address formed per step
+    const char* gbase = lds_at(c, (p0 + 1) * 4096);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const u32x4* nb = reinterpret_cast<const u32x4*>(
-            (FV & 2) ? gbase + r * 4096 : lds_at(c, (p0 + r + 1) * 4096));
+        const u32x4* nb = reinterpret_cast<const u32x4*>(gbase + r * 4096);
         const u32x4 a0 = c.ring[r][0], a1 = c.ring[r][1];
         const int k = K0 + r;
         // the step's VALU (epilogue: AGPR reads, cvt, ReLU, LDS address) 2 per MFMA gap, 4 in
@@ -423,22 +413,22 @@ __device__ __forceinline__ void group4(FCtx<FV>& c, f32x16 (&acc)[2][4], const f
 
 // 16 k-steps from position p0 carrying the 16 epilogue units of the other set; BAR: the
 // window's closing barrier inside its step 15
-template <typename T, int EK, bool BAR, int FV>
-__device__ __forceinline__ void steps16e(FCtx<FV>& c, f32x16 (&acc)[2][4],
+template <typename T, int EK, bool BAR>
+__device__ __forceinline__ void steps16e(FCtx& c, f32x16 (&acc)[2][4],
                                          const f32x16 (&accY)[2][4], int p0) {
-    group4<T, EK, 0, -1, FV>(c, acc, accY, p0);
-    group4<T, EK, 4, -1, FV>(c, acc, accY, p0 + 4);
-    group4<T, EK, 8, -1, FV>(c, acc, accY, p0 + 8);
-    group4<T, EK, 12, BAR ? 3 : -1, FV>(c, acc, accY, p0 + 12);
+    group4<T, EK, 0, -1>(c, acc, accY, p0);
+    group4<T, EK, 4, -1>(c, acc, accY, p0 + 4);
+    group4<T, EK, 8, -1>(c, acc, accY, p0 + 8);
+    group4<T, EK, 12, BAR ? 3 : -1>(c, acc, accY, p0 + 12);
 }
 
 // plain k-steps [j0, j1) from position pos0 as ONE runtime loop of 4-step groups (code size:
 // the kernel must stay well inside the instruction cache)
-template <typename T, int FV>
-__device__ __forceinline__ void steps_plain(FCtx<FV>& c, f32x16 (&acc)[2][4],
+template <typename T>
+__device__ __forceinline__ void steps_plain(FCtx& c, f32x16 (&acc)[2][4],
                                             const f32x16 (&accY)[2][4], int pos0, int j0, int j1) {
 #pragma unroll 1
-    for (int j = j0; j < j1; j += 4) group4<T, FE_NONE, 0, -1, FV>(c, acc, accY, pos0 + j);
+    for (int j = j0; j < j1; j += 4) group4<T, FE_NONE, 0, -1>(c, acc, accY, pos0 + j);
 }
 
 // One part: the aux step, then nk ring steps reading positions pos0 .. pos0 + nk - 1 = 31
@@ -452,8 +442,8 @@ __device__ __forceinline__ void steps_plain(FCtx<FV>& c, f32x16 (&acc)[2][4],
 //     every wave / no wave reads the early positions any more before E16 writes them);
 //     `endbar` (E work parts): the barrier inside the part's last step, publishing the window's
 //     writes to the next part, whose aux step then reads on without a barrier.
-template <typename T, int EK, bool E16, int FV>
-__device__ __forceinline__ void run_part(FCtx<FV>& c, f32x16 (&acc)[2][4], const f32x16 (&accY)[2][4],
+template <typename T, int EK, bool E16>
+__device__ __forceinline__ void run_part(FCtx& c, f32x16 (&acc)[2][4], const f32x16 (&accY)[2][4],
                                          int nk, bool mid, bool endbar, FSrc naux, int pos0,
                                          bool bar0) {
     const f32x16 zero = {};
@@ -503,13 +493,13 @@ __device__ __forceinline__ void run_part(FCtx<FV>& c, f32x16 (&acc)[2][4], const
         stamp(c);
         if (endbar && nk == 32) {       // the end barrier inside step 31
             steps_plain<T>(c, acc, accY, pos0, 16, 28);
-            group4<T, FE_NONE, 0, 3, FV>(c, acc, accY, pos0 + 28);
+            group4<T, FE_NONE, 0, 3>(c, acc, accY, pos0 + 28);
         } else {
             steps_plain<T>(c, acc, accY, pos0, 16, nk);
         }
     } else if (E16) {                   // nk 32, mid
         steps_plain<T>(c, acc, accY, pos0, 0, 12);
-        group4<T, FE_NONE, 0, 3, FV>(c, acc, accY, pos0 + 12);
+        group4<T, FE_NONE, 0, 3>(c, acc, accY, pos0 + 12);
         stamp(c);
         if (endbar) steps16e<T, EK, true>(c, acc, accY, pos0 + 16);
         else steps16e<T, EK, false>(c, acc, accY, pos0 + 16);
@@ -523,8 +513,8 @@ __device__ __forceinline__ void run_part(FCtx<FV>& c, f32x16 (&acc)[2][4], const
 
 // a whole set into this wave's early (LATE = false) or late positions 16u + 4w + 2i + s
 // (serial: layer 0, layer 3 at skip 253); the per-wave base and immediates per tile
-template <typename T, bool LATE, int FV>
-__device__ __forceinline__ void acc_to_lds(FCtx<FV>& c, const f32x16 (&acc)[2][4]) {
+template <typename T, bool LATE>
+__device__ __forceinline__ void acc_to_lds(FCtx& c, const f32x16 (&acc)[2][4]) {
     u32x4* p = act_w(c, LATE ? 16 : 0);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -537,10 +527,10 @@ __device__ __forceinline__ void acc_to_lds(FCtx<FV>& c, const f32x16 (&acc)[2][4
         }
 }
 
-template <typename T, int S, bool POINTS, int FV>
+template <typename T, int S, bool POINTS>
 __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[kFsLds];
-    FCtx<FV> c;
+    FCtx c;
     c.lane = threadIdx.x & 63;
     c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     c.h = c.lane >> 5;
@@ -634,56 +624,56 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
         // ---- layer 0 (aux only), both parts through set A into LDS serially (set B still
         // holds the previous tile's layer 7 part 1, folded into the output during L1p0); the
         // previous tile's readers all passed the end barrier of its layer 7
-        run_part<T, FE_NONE, false, FV>(c, accA, accB, 0, false, false, shp(1), 0, false);
-        acc_to_lds<T, false, FV>(c, accA);
+        run_part<T, FE_NONE, false>(c, accA, accB, 0, false, false, shp(1), 0, false);
+        acc_to_lds<T, false>(c, accA);
         stamp(c);
-        run_part<T, FE_NONE, false, FV>(c, accA, accB, 0, false, false, bias(2), 0, false);
-        acc_to_lds<T, true, FV>(c, accA);
+        run_part<T, FE_NONE, false>(c, accA, accB, 0, false, false, bias(2), 0, false);
+        acc_to_lds<T, true>(c, accA);
         stamp(c);
 
         // ---- two-part layers 1, 2 (and 3 when 512 wide).  L1p0 folds the previous tile's
         // layer 7 part 1 into its outputs (FE_FIN1); p1 of layer l publishes with its end barrier
         int pi = 2;
-        run_part<T, FE_FIN1, false, FV>(c, accA, accB, 32, true, false, bias(pi + 1), 0, true);
-        run_part<T, FE_EARLY, true, FV>(c, accB, accA, 32, true, true, bias(pi + 2), 0, false);
+        run_part<T, FE_FIN1, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0, true);
+        run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0, false);
         pi += 2;
         constexpr int L2P = S == 256 ? 3 : 4;
 #pragma unroll 1
         for (int l = 2; l < L2P; ++l, pi += 2) {
             // the part after layer 3 (512 wide) is layer 4's: per-shape aux
             const FSrc nx = (S == 512 && l == 3) ? shp(2) : bias(pi + 2);
-            run_part<T, FE_LATE, false, FV>(c, accA, accB, 32, true, false, bias(pi + 1), 0, false);
-            run_part<T, FE_EARLY, true, FV>(c, accB, accA, 32, true, true, nx, 0, false);
+            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0, false);
+            run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, nx, 0, false);
         }
         if (S == 256) {
             // layer 3: one part of rows 64w..64w+63 -> positions 16 + 4w + 2i + s (serial,
             // once every wave is done reading layer 3's inputs)
-            run_part<T, FE_LATE, false, FV>(c, accA, accB, 32, true, false, shp(2), 0, false);
+            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, shp(2), 0, false);
             fs_bar();
-            acc_to_lds<T, true, FV>(c, accA);
+            acc_to_lds<T, true>(c, accA);
             stamp(c);
             // layer 4 (K = 256, positions 16..31); part 0 -> early positions during part 1
-            run_part<T, FE_NONE, false, FV>(c, accA, accB, 16, false, false, shp(3), 16, true);
-            run_part<T, FE_EARLY, false, FV>(c, accB, accA, 16, false, true, bias(pi + 3), 16,
+            run_part<T, FE_NONE, false>(c, accA, accB, 16, false, false, shp(3), 16, true);
+            run_part<T, FE_EARLY, false>(c, accB, accA, 16, false, true, bias(pi + 3), 16,
                                              false);
             pi += 3;
         } else {
-            run_part<T, FE_LATE, false, FV>(c, accA, accB, 32, true, false, shp(3), 0, false);
-            run_part<T, FE_EARLY, true, FV>(c, accB, accA, 32, true, true, bias(pi + 2), 0, false);
+            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, shp(3), 0, false);
+            run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0, false);
             pi += 2;
         }
         // ---- layers 5, 6
 #pragma unroll 1
         for (int l = 5; l < 7; ++l, pi += 2) {
-            run_part<T, FE_LATE, false, FV>(c, accA, accB, 32, true, false, bias(pi + 1), 0, false);
-            run_part<T, FE_EARLY, true, FV>(c, accB, accA, 32, true, true, bias(pi + 2), 0, false);
+            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0, false);
+            run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0, false);
         }
         // ---- layer 7: part 0 folds into the dot product during part 1, part 1 during the
         // next tile's L1p0 (its end barrier lets the next tile overwrite every position)
-        run_part<T, FE_LATE, false, FV>(c, accA, accB, 32, true, false, bias(pi + 1), 0, false);
+        run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0, false);
         // (no prefetch of the next tile's first aux fragments here: live across the whole
         // part they were spilled, each spill waiting for the whole ring)
-        run_part<T, FE_FIN0, false, FV>(c, accB, accA, 32, false, true, FSrc{true, 0, true}, 0,
+        run_part<T, FE_FIN0, false>(c, accB, accA, 32, false, true, FSrc{true, 0, true}, 0,
                                         false);
         c.prev_shape = shape;
         c.prev_local = local;
@@ -708,25 +698,12 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
     }
 }
 
-template <typename T, int S, int D>
-void launch_fs_d(const FArgs& a, bool points, hipStream_t s, int grid) {
-    if (points)
-        hipLaunchKernelGGL((dec_fs_kernel<T, S, true, D>), dim3(grid), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((dec_fs_kernel<T, S, false, D>), dim3(grid), dim3(256), 0, s, a);
-}
-
 template <typename T, int S>
 void launch_fs(const FArgs& a, bool points, hipStream_t s, int grid) {
-#ifdef LDM_DEV_KNOBS
-    switch (dev_knob("LDM_FS_V", kFsDefaultV)) {
-        case 0: return launch_fs_d<T, S, 0>(a, points, s, grid);
-        case 1: return launch_fs_d<T, S, 1>(a, points, s, grid);
-        case 3: return launch_fs_d<T, S, 3>(a, points, s, grid);
-        default: break;
-    }
-#endif
-    launch_fs_d<T, S, kFsDefaultV>(a, points, s, grid);
+    if (points)
+        hipLaunchKernelGGL((dec_fs_kernel<T, S, true>), dim3(grid), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((dec_fs_kernel<T, S, false>), dim3(grid), dim3(256), 0, s, a);
 }
 
 }  // namespace

@@ -6,14 +6,17 @@
 //   mse_loss_kernel         A9 eps-MSE loss and its gradient (deterministic single-block sum)
 //   small_linear_kernel     A6 for the sampling batch (B <= 16): one wave per output row,
 //                           activations staged once in LDS, k split over the 64 lanes, wave
-//                           shuffle reduction, fused epilogue (bias | residual+SiLU+E[t] |
-//                           out-projection + DDPM step).  VALU fp32 accumulate; MFMA is kept
-//                           for the decoder (north star).
+//                           shuffle reduce-scatter (gemv_row.h, shared with sample_loop.hip),
+//                           fused epilogue (bias | residual+SiLU+E[t] | out-projection + DDPM
+//                           step).  VALU fp32 accumulate; MFMA is kept for the decoder (north
+//                           star).  Its three earlier forms are retired: DESIGN.md §5
+//                           "Retired build knobs".
 //   linear_tiled_kernel     A6/A7 for training batches: 64x64 register-tiled VALU GEMM with
 //                           LDS-staged operand tiles, arbitrary strides (X W^T, G W, G^T X).
 //   silu_bwd / colsum / gather_rows   A7 elementwise pieces, A5 embedding lookup.
 #include "ldm_internal.h"
 #include "ddpm_common.h"
+#include "gemv_row.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -118,312 +121,18 @@ struct SmallArgs {
 
 constexpr int kSmallMaxB = 16;
 
-template <typename TW, int EPI>
+// One wave per output row, 4 rows per 256-thread block.  The row's weight loads (gemv_row.h
+// load_row: NJ = ceil(K / 8 / 64) chunks per lane, K <= 2048) are issued BEFORE the activation
+// staging and its barrier so the two memory latencies overlap; the staging is batched 8 x 16 B
+// per thread before any LDS store; row_dot reduce-scatters over the MB samples.  The row
+// arithmetic is shared with the persistent loop (sample_loop.hip) through gemv_row.h.
+template <typename TW, int EPI, int MB, int NJ>
 __global__ __launch_bounds__(256) void small_linear_kernel(SmallArgs a) {
     extern __shared__ __attribute__((aligned(16))) float xs[];   // [B][K]
-    const int nx = a.B * a.K;
-    for (int i = threadIdx.x * 4; i < nx; i += 256 * 4)
-        *reinterpret_cast<f32x4*>(xs + i) = *reinterpret_cast<const f32x4*>(a.X + i);
-    __syncthreads();
     const int lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (m >= a.M) return;
-    float acc[kSmallMaxB];
-#pragma unroll
-    for (int b = 0; b < kSmallMaxB; ++b) acc[b] = 0.f;
-    const int nch = a.K >> 3;   // 8-element chunks
-    for (int c = lane; c < nch; c += 64) {
-        float w[8];
-        if (sizeof(TW) == 2) {
-            const uint4 u = *reinterpret_cast<const uint4*>(
-                reinterpret_cast<const unsigned short*>(a.W) + (size_t)m * a.ldw + c * 8);
-            w[0] = bf16_to_f32(u.x & 0xffff); w[1] = bf16_to_f32(u.x >> 16);
-            w[2] = bf16_to_f32(u.y & 0xffff); w[3] = bf16_to_f32(u.y >> 16);
-            w[4] = bf16_to_f32(u.z & 0xffff); w[5] = bf16_to_f32(u.z >> 16);
-            w[6] = bf16_to_f32(u.w & 0xffff); w[7] = bf16_to_f32(u.w >> 16);
-        } else {
-            const float* wp = reinterpret_cast<const float*>(a.W) + (size_t)m * a.ldw + c * 8;
-            const f32x4 w0 = *reinterpret_cast<const f32x4*>(wp);
-            const f32x4 w1 = *reinterpret_cast<const f32x4*>(wp + 4);
-            w[0] = w0[0]; w[1] = w0[1]; w[2] = w0[2]; w[3] = w0[3];
-            w[4] = w1[0]; w[5] = w1[1]; w[6] = w1[2]; w[7] = w1[3];
-        }
-#pragma unroll
-        for (int b = 0; b < kSmallMaxB; ++b) {
-            if (b < a.B) {
-                const f32x4 x0 = *reinterpret_cast<const f32x4*>(xs + b * a.K + c * 8);
-                const f32x4 x1 = *reinterpret_cast<const f32x4*>(xs + b * a.K + c * 8 + 4);
-                float s = acc[b];
-                s = fmaf(w[0], x0[0], s); s = fmaf(w[1], x0[1], s);
-                s = fmaf(w[2], x0[2], s); s = fmaf(w[3], x0[3], s);
-                s = fmaf(w[4], x1[0], s); s = fmaf(w[5], x1[1], s);
-                s = fmaf(w[6], x1[2], s); s = fmaf(w[7], x1[3], s);
-                acc[b] = s;
-            }
-        }
-    }
-    float mine = 0.f;   // lane b keeps row b's total
-#pragma unroll
-    for (int b = 0; b < kSmallMaxB; ++b) {
-        if (b < a.B) {
-            float v = acc[b];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-            if (lane == b) mine = v;
-        }
-    }
-    if (lane < a.B) {
-        const int b = lane;
-        const float pre = mine + a.bias[m];
-        if (EPI == SE_BIAS) {
-            a.Y[(size_t)b * a.M + m] = pre;
-        } else if (EPI == SE_BLOCK) {
-            a.Y[(size_t)b * a.M + m] = xs[b * a.K + m] + silu(pre);
-        } else {
-            const size_t i = (size_t)b * a.M + m;
-            const bool noise = a.t > 0;
-            a.Y[i] = ddpm_update(a.xlat[i], pre, noise ? a.z[i] : 0.f, a.c1t[a.t], a.c2t[a.t],
-                                 a.sgt[a.t], noise);
-        }
-    }
-}
-
-// v2: one wave per block owns R rows.  All weight and activation loads are issued up front
-// (registers, no LDS staging, no barrier), then R*MB partial dot products per lane are
-// reduce-scattered across the wave (each butterfly level exchanges only the half a lane gives
-// away: 32 shuffles for 4 rows x 8 samples instead of 192), and the lanes that end up owning a
-// (row, sample) total run the fused epilogue.  Latency-bound by design.
-template <typename TW, int EPI, int R, int MB>
-__global__ __launch_bounds__(64) void small_linear_v2(SmallArgs a) {
-    constexpr int V = R * MB;                 // values to reduce per lane (power of 2, <= 64)
-    static_assert((V & (V - 1)) == 0 && V <= 64, "R*MB must be a power of two <= 64");
-    const int lane = threadIdx.x;
-    const int m0 = blockIdx.x * R;
-    const int nch = a.K >> 3;                 // 8-element chunks; lane takes c = lane + 64 j
-    constexpr int MAXJ = 4;                   // K <= 2048
-    float acc[V];
-#pragma unroll
-    for (int i = 0; i < V; ++i) acc[i] = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAXJ; ++j) {
-        const int c = lane + 64 * j;
-        if (64 * j >= nch) break;             // uniform
-        const bool on = c < nch;
-        float w[R][8];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int m = (m0 + r < a.M) ? m0 + r : a.M - 1;
-            if (sizeof(TW) == 2) {
-                uint4 u = {0, 0, 0, 0};
-                if (on) u = *reinterpret_cast<const uint4*>(
-                    reinterpret_cast<const unsigned short*>(a.W) + (size_t)m * a.ldw + c * 8);
-                w[r][0] = bf16_to_f32(u.x & 0xffff); w[r][1] = bf16_to_f32(u.x >> 16);
-                w[r][2] = bf16_to_f32(u.y & 0xffff); w[r][3] = bf16_to_f32(u.y >> 16);
-                w[r][4] = bf16_to_f32(u.z & 0xffff); w[r][5] = bf16_to_f32(u.z >> 16);
-                w[r][6] = bf16_to_f32(u.w & 0xffff); w[r][7] = bf16_to_f32(u.w >> 16);
-            } else {
-                f32x4 w0 = {0, 0, 0, 0}, w1 = {0, 0, 0, 0};
-                if (on) {
-                    const float* wp = reinterpret_cast<const float*>(a.W) + (size_t)m * a.ldw + c * 8;
-                    w0 = *reinterpret_cast<const f32x4*>(wp);
-                    w1 = *reinterpret_cast<const f32x4*>(wp + 4);
-                }
-                w[r][0] = w0[0]; w[r][1] = w0[1]; w[r][2] = w0[2]; w[r][3] = w0[3];
-                w[r][4] = w1[0]; w[r][5] = w1[1]; w[r][6] = w1[2]; w[r][7] = w1[3];
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < MB; ++b) {
-            f32x4 x0 = {0, 0, 0, 0}, x1 = {0, 0, 0, 0};
-            if (on && b < a.B) {
-                x0 = *reinterpret_cast<const f32x4*>(a.X + (size_t)b * a.K + c * 8);
-                x1 = *reinterpret_cast<const f32x4*>(a.X + (size_t)b * a.K + c * 8 + 4);
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                float s = acc[r * MB + b];
-                s = fmaf(w[r][0], x0[0], s); s = fmaf(w[r][1], x0[1], s);
-                s = fmaf(w[r][2], x0[2], s); s = fmaf(w[r][3], x0[3], s);
-                s = fmaf(w[r][4], x1[0], s); s = fmaf(w[r][5], x1[1], s);
-                s = fmaf(w[r][6], x1[2], s); s = fmaf(w[r][7], x1[3], s);
-                acc[r * MB + b] = s;
-            }
-        }
-    }
-    // reduce-scatter: at level lv (offset o = 32 >> lv) a lane keeps the half of its n = V >> lv
-    // values selected by lane & o and adds its partner's copy of that half.
-#pragma unroll
-    for (int lv = 0; lv < 6; ++lv) {
-        const int o = 32 >> lv;
-        const int n = V >> lv;                // compile-time after unrolling
-        const bool upper = (lane & o) != 0;
-        if (n > 1) {
-            const int half = n >> 1;
-#pragma unroll
-            for (int i = 0; i < half; ++i) {
-                const float send = upper ? acc[i] : acc[i + half];
-                const float keep = upper ? acc[i + half] : acc[i];
-                acc[i] = keep + xor_lane(send, o, lane);
-            }
-        } else {
-            acc[0] += xor_lane(acc[0], o, lane);
-        }
-    }
-    // lane owns value index idx = (lane >> (6 - log2 V)) in natural order: idx = r*MB + b
-    constexpr int LV = (V >= 64) ? 6 : (V >= 32) ? 5 : (V >= 16) ? 4 : (V >= 8) ? 3 : (V >= 4) ? 2 : (V >= 2) ? 1 : 0;
-    const int idx = lane >> (6 - LV);
-    const bool writer = (lane & ((1 << (6 - LV)) - 1)) == 0;
-    const int r = idx / MB, b = idx - (idx / MB) * MB;
-    const int m = m0 + r;
-    if (writer && b < a.B && m < a.M) {
-        const float pre = acc[0] + a.bias[m];
-        const size_t i = (size_t)b * a.M + m;
-        if (EPI == SE_BIAS) {
-            a.Y[i] = pre;
-        } else if (EPI == SE_BLOCK) {
-            a.Y[i] = a.X[(size_t)b * a.K + m] + silu(pre);
-        } else {
-            const bool noise = a.t > 0;
-            a.Y[i] = ddpm_update(a.xlat[i], pre, noise ? a.z[i] : 0.f, a.c1t[a.t], a.c2t[a.t],
-                                 a.sgt[a.t], noise);
-        }
-    }
-}
-
-// v3: v1's shape (one wave per output row, 4 rows per 256-thread block, activations staged
-// once per block in LDS) with the row's weight loads issued BEFORE the activation staging and
-// its barrier (the two memory latencies overlap), and a reduce-scatter over the MB samples.
-template <typename TW, int EPI, int MB>
-__global__ __launch_bounds__(256) void small_linear_v3(SmallArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float xs[];   // [B][K]
-    const int lane = threadIdx.x & 63;
-    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int mm = m < a.M ? m : a.M - 1;
-    const int nch = a.K >> 3;
-    constexpr int MAXJ = 4;                    // K <= 2048
-    float w[MAXJ][8];
-#pragma unroll
-    for (int j = 0; j < MAXJ; ++j) {
-        const int c = lane + 64 * j;
-        const bool on = c < nch;
-        if (sizeof(TW) == 2) {
-            uint4 u = {0, 0, 0, 0};
-            if (on) u = *reinterpret_cast<const uint4*>(
-                reinterpret_cast<const unsigned short*>(a.W) + (size_t)mm * a.ldw + c * 8);
-            w[j][0] = bf16_to_f32(u.x & 0xffff); w[j][1] = bf16_to_f32(u.x >> 16);
-            w[j][2] = bf16_to_f32(u.y & 0xffff); w[j][3] = bf16_to_f32(u.y >> 16);
-            w[j][4] = bf16_to_f32(u.z & 0xffff); w[j][5] = bf16_to_f32(u.z >> 16);
-            w[j][6] = bf16_to_f32(u.w & 0xffff); w[j][7] = bf16_to_f32(u.w >> 16);
-        } else {
-            f32x4 w0 = {0, 0, 0, 0}, w1 = {0, 0, 0, 0};
-            if (on) {
-                const float* wp = reinterpret_cast<const float*>(a.W) + (size_t)mm * a.ldw + c * 8;
-                w0 = *reinterpret_cast<const f32x4*>(wp);
-                w1 = *reinterpret_cast<const f32x4*>(wp + 4);
-            }
-            w[j][0] = w0[0]; w[j][1] = w0[1]; w[j][2] = w0[2]; w[j][3] = w0[3];
-            w[j][4] = w1[0]; w[j][5] = w1[1]; w[j][6] = w1[2]; w[j][7] = w1[3];
-        }
-    }
-    const int nx = a.B * a.K;
-    for (int i = threadIdx.x * 4; i < nx; i += 256 * 4)
-        *reinterpret_cast<f32x4*>(xs + i) = *reinterpret_cast<const f32x4*>(a.X + i);
-    __syncthreads();
-    float acc[MB];
-#pragma unroll
-    for (int b = 0; b < MB; ++b) acc[b] = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAXJ; ++j) {
-        const int c = lane + 64 * j;
-        if (64 * j >= nch) break;
-        if (c < nch) {
-#pragma unroll
-            for (int b = 0; b < MB; ++b) {
-                if (b < a.B) {
-                    const f32x4 x0 = *reinterpret_cast<const f32x4*>(xs + b * a.K + c * 8);
-                    const f32x4 x1 = *reinterpret_cast<const f32x4*>(xs + b * a.K + c * 8 + 4);
-                    float t = acc[b];
-                    t = fmaf(w[j][0], x0[0], t); t = fmaf(w[j][1], x0[1], t);
-                    t = fmaf(w[j][2], x0[2], t); t = fmaf(w[j][3], x0[3], t);
-                    t = fmaf(w[j][4], x1[0], t); t = fmaf(w[j][5], x1[1], t);
-                    t = fmaf(w[j][6], x1[2], t); t = fmaf(w[j][7], x1[3], t);
-                    acc[b] = t;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int lv = 0; lv < 6; ++lv) {
-        const int o = 32 >> lv;
-        const int n = MB >> lv;
-        const bool upper = (lane & o) != 0;
-        if (n > 1) {
-            const int half = n >> 1;
-#pragma unroll
-            for (int i = 0; i < half; ++i) {
-                const float send = upper ? acc[i] : acc[i + half];
-                const float keep = upper ? acc[i + half] : acc[i];
-                acc[i] = keep + xor_lane(send, o, lane);
-            }
-        } else {
-            acc[0] += xor_lane(acc[0], o, lane);
-        }
-    }
-    constexpr int LB = (MB >= 16) ? 4 : 3;
-    const int b = lane >> (6 - LB);
-    const bool writer = (lane & ((1 << (6 - LB)) - 1)) == 0;
-    if (m < a.M && writer && b < a.B) {
-        const float pre = acc[0] + a.bias[m];
-        const size_t i = (size_t)b * a.M + m;
-        if (EPI == SE_BIAS) {
-            a.Y[i] = pre;
-        } else if (EPI == SE_BLOCK) {
-            a.Y[i] = xs[b * a.K + m] + silu(pre);
-        } else {
-            const bool noise = a.t > 0;
-            a.Y[i] = ddpm_update(a.xlat[i], pre, noise ? a.z[i] : 0.f, a.c1t[a.t], a.c2t[a.t],
-                                 a.sgt[a.t], noise);
-        }
-    }
-}
-
-// v4: v3 with every global load unconditional (index clamped, value selected afterwards) so a
-// wave issues all of its loads back to back -- a load under a divergent branch makes hipcc
-// wait vmcnt(0) before leaving the branch, one round trip per load -- and the activation
-// staging batched 8 x 16 B per thread before any LDS store.  NJ = ceil(K / 8 / 64) weight
-// chunks per lane (K <= 2048).
-template <typename TW, int EPI, int MB, int NJ>
-__global__ __launch_bounds__(256) void small_linear_v4(SmallArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float xs[];   // [B][K]
-    const int lane = threadIdx.x & 63;
-    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int mm = m < a.M ? m : a.M - 1;
-    const int nch = a.K >> 3;
     float w[NJ][8];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int c = lane + 64 * j;
-        const bool on = c < nch;
-        const size_t off = (size_t)mm * a.ldw + (on ? c : 0) * 8;
-        if constexpr (sizeof(TW) == 2) {
-            uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(a.W) + off);
-            const unsigned q[4] = {on ? u.x : 0u, on ? u.y : 0u, on ? u.z : 0u, on ? u.w : 0u};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                w[j][2 * i] = __builtin_bit_cast(float, q[i] << 16);
-                w[j][2 * i + 1] = __builtin_bit_cast(float, q[i] & 0xffff0000u);
-            }
-        } else {
-            const float* wp = reinterpret_cast<const float*>(a.W) + off;
-            const f32x4 w0 = *reinterpret_cast<const f32x4*>(wp);
-            const f32x4 w1 = *reinterpret_cast<const f32x4*>(wp + 4);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                w[j][i] = on ? w0[i] : 0.f;
-                w[j][4 + i] = on ? w1[i] : 0.f;
-            }
-        }
-    }
+    load_row<TW, NJ>(w, a.W, m < a.M ? m : a.M - 1, a.ldw, a.K, lane);
     const int n4 = (a.B * a.K) >> 2;
     const f32x4* X4 = reinterpret_cast<const f32x4*>(a.X);
     for (int base = 0; base < n4; base += 256 * 8) {
@@ -440,48 +149,12 @@ __global__ __launch_bounds__(256) void small_linear_v4(SmallArgs a) {
         }
     }
     __syncthreads();
-    float acc[MB];
-#pragma unroll
-    for (int b = 0; b < MB; ++b) acc[b] = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int c = lane + 64 * j;
-        const int cc = c < nch ? c : 0;       // off lanes: zero weights times a valid row
-#pragma unroll
-        for (int b = 0; b < MB; ++b) {
-            const int bb = b < a.B ? b : 0;   // rows past B are never written out
-            const f32x4 x0 = *reinterpret_cast<const f32x4*>(xs + bb * a.K + cc * 8);
-            const f32x4 x1 = *reinterpret_cast<const f32x4*>(xs + bb * a.K + cc * 8 + 4);
-            float t = acc[b];
-            t = fmaf(w[j][0], x0[0], t); t = fmaf(w[j][1], x0[1], t);
-            t = fmaf(w[j][2], x0[2], t); t = fmaf(w[j][3], x0[3], t);
-            t = fmaf(w[j][4], x1[0], t); t = fmaf(w[j][5], x1[1], t);
-            t = fmaf(w[j][6], x1[2], t); t = fmaf(w[j][7], x1[3], t);
-            acc[b] = t;
-        }
-    }
-#pragma unroll
-    for (int lv = 0; lv < 6; ++lv) {
-        const int o = 32 >> lv;
-        const int n = MB >> lv;
-        const bool upper = (lane & o) != 0;
-        if (n > 1) {
-            const int half = n >> 1;
-#pragma unroll
-            for (int i = 0; i < half; ++i) {
-                const float send = upper ? acc[i] : acc[i + half];
-                const float keep = upper ? acc[i + half] : acc[i];
-                acc[i] = keep + xor_lane(send, o, lane);
-            }
-        } else {
-            acc[0] += xor_lane(acc[0], o, lane);
-        }
-    }
+    const float dot = row_dot<MB, NJ>(w, xs, a.B, a.K, lane);
     constexpr int LB = (MB >= 16) ? 4 : 3;
     const int b = lane >> (6 - LB);
     const bool writer = (lane & ((1 << (6 - LB)) - 1)) == 0;
     if (m < a.M && writer && b < a.B) {
-        const float pre = acc[0] + a.bias[m];
+        const float pre = dot + a.bias[m];
         const size_t i = (size_t)b * a.M + m;
         if (EPI == SE_BIAS) {
             a.Y[i] = pre;
@@ -496,70 +169,25 @@ __global__ __launch_bounds__(256) void small_linear_v4(SmallArgs a) {
 }
 
 template <typename TW, int EPI, int MB>
-void launch_small_v4_nj(const SmallArgs& a, hipStream_t s) {
+void launch_small_nj(const SmallArgs& a, hipStream_t s) {
     const size_t lds = (size_t)a.B * a.K * sizeof(float);
     const dim3 grid((a.M + 3) / 4);
     const int nj = ((a.K >> 3) + 63) / 64;
-    if (nj <= 1) hipLaunchKernelGGL((small_linear_v4<TW, EPI, MB, 1>), grid, dim3(256), lds, s, a);
-    else if (nj <= 2) hipLaunchKernelGGL((small_linear_v4<TW, EPI, MB, 2>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((small_linear_v4<TW, EPI, MB, 4>), grid, dim3(256), lds, s, a);
+    if (nj <= 1) hipLaunchKernelGGL((small_linear_kernel<TW, EPI, MB, 1>), grid, dim3(256), lds, s, a);
+    else if (nj <= 2) hipLaunchKernelGGL((small_linear_kernel<TW, EPI, MB, 2>), grid, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((small_linear_kernel<TW, EPI, MB, 4>), grid, dim3(256), lds, s, a);
 }
 
 template <typename TW, int EPI>
-void launch_small_v4(const SmallArgs& a, hipStream_t s) {
-    if (a.B <= 8) launch_small_v4_nj<TW, EPI, 8>(a, s);
-    else launch_small_v4_nj<TW, EPI, 16>(a, s);
-}
-
-template <typename TW, int EPI>
-void launch_small_v3(const SmallArgs& a, hipStream_t s) {
-    const size_t lds = (size_t)a.B * a.K * sizeof(float);
-    const dim3 grid((a.M + 3) / 4);
-    if (a.B <= 8)
-        hipLaunchKernelGGL((small_linear_v3<TW, EPI, 8>), grid, dim3(256), lds, s, a);
-    else
-        hipLaunchKernelGGL((small_linear_v3<TW, EPI, 16>), grid, dim3(256), lds, s, a);
-}
-
-int small_version() {
-    const int v = dev_knob("LDM_SMALL_LINEAR", 4);   // development A/B knob: 1, 2, 3, 4 (default)
-    return (v >= 1 && v <= 4) ? v : 4;
-}
-
-template <typename TW, int EPI>
-void launch_small_v2(const SmallArgs& a, hipStream_t s) {
-    constexpr int R = 4;
-    const dim3 grid((a.M + R - 1) / R);
-    if (a.B <= 8)
-        hipLaunchKernelGGL((small_linear_v2<TW, EPI, R, 8>), grid, dim3(64), 0, s, a);
-    else
-        hipLaunchKernelGGL((small_linear_v2<TW, EPI, R, 16>), grid, dim3(64), 0, s, a);
+void launch_small_mb(const SmallArgs& a, hipStream_t s) {
+    if (a.B <= 8) launch_small_nj<TW, EPI, 8>(a, s);
+    else launch_small_nj<TW, EPI, 16>(a, s);
 }
 
 template <int EPI>
 int launch_small(const SmallArgs& a, int w_dtype, hipStream_t s) {
-    const int ver = small_version();
-    if (ver == 2) {
-        if (w_dtype == LDM_BF16) launch_small_v2<unsigned short, EPI>(a, s);
-        else launch_small_v2<float, EPI>(a, s);
-        return launch_status("small_linear_v2");
-    }
-    if (ver == 4) {
-        if (w_dtype == LDM_BF16) launch_small_v4<unsigned short, EPI>(a, s);
-        else launch_small_v4<float, EPI>(a, s);
-        return launch_status("small_linear_v4");
-    }
-    if (ver == 3) {
-        if (w_dtype == LDM_BF16) launch_small_v3<unsigned short, EPI>(a, s);
-        else launch_small_v3<float, EPI>(a, s);
-        return launch_status("small_linear_v3");
-    }
-    const size_t lds = (size_t)a.B * a.K * sizeof(float);
-    const dim3 grid((a.M + 3) / 4);
-    if (w_dtype == LDM_BF16)
-        hipLaunchKernelGGL((small_linear_kernel<unsigned short, EPI>), grid, dim3(256), lds, s, a);
-    else
-        hipLaunchKernelGGL((small_linear_kernel<float, EPI>), grid, dim3(256), lds, s, a);
+    if (w_dtype == LDM_BF16) launch_small_mb<unsigned short, EPI>(a, s);
+    else launch_small_mb<float, EPI>(a, s);
     return launch_status("small_linear");
 }
 

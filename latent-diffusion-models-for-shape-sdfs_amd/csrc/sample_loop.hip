@@ -1,7 +1,7 @@
 // A10 as ONE launch: the whole T-step DDPM reverse loop of the MLP denoiser in a persistent,
 // kernel whose whole grid is resident (SURVEY.md §8(a) A6 + A8 + A10).
 //
-// Why: the graph-replayed loop (denoiser.hip small_linear_v4) is 6 dependent launches per step
+// Why: the graph-replayed loop (denoiser.hip small_linear_kernel) is 6 dependent launches per step
 // at the ~5 us floor of a dependent launch; the GEMVs themselves are far from any bandwidth
 // limit.  Here the grid is H/4 workgroups of 4 waves, one wave per output row, and
 //   * every wave keeps ITS weight rows in registers for the whole loop (in-proj row, one row of
@@ -11,8 +11,9 @@
 //     atomic per workgroup, sc1 polling with s_sleep, sc1 loads of the activations) instead of
 //     a kernel boundary;
 //   * per layer each workgroup stages the [B][K] activations into LDS once.
-// Arithmetic is the v4 GEMV's exactly (same k-to-lane mapping, same fma order, same shuffle
-// reduce-scatter, same epilogues), so the loop is bit-identical to the graph path
+// The row arithmetic is the per-step GEMV's by construction: both call gemv_row.h's load_row and
+// row_dot (k-to-lane mapping, fma order, shuffle reduce-scatter), and the epilogues are the same,
+// so the loop is bit-identical to the graph path
 // (tests/test_gpu_ddpm.py::test_sample_loop_persistent_matches_graph).
 //
 // Termination: every barrier wait is bounded (kSpinLimit polls); a workgroup that times out
@@ -20,6 +21,7 @@
 // sees LDM_ETIMEOUT-style failure through the status word instead of a hung GPU.
 #include "ldm_internal.h"
 #include "ddpm_common.h"
+#include "gemv_row.h"
 #include "loop_sync.h"
 
 #include <stdlib.h>
@@ -61,36 +63,6 @@ struct LoopArgs {
     int tagged;              // replica loop: 1 = tagged-granule hand-offs, 0 = XCD barriers
 };
 
-template <typename TW, int NJ>
-__device__ __forceinline__ void load_row(float (&w)[NJ][8], const void* W, int row, int ldw,
-                                         int K, int lane) {
-    const int nch = K >> 3;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int c = lane + 64 * j;
-        const bool on = c < nch;
-        const size_t off = (size_t)row * ldw + (on ? c : 0) * 8;
-        if constexpr (sizeof(TW) == 2) {
-            uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(W) + off);
-            const unsigned q[4] = {on ? u.x : 0u, on ? u.y : 0u, on ? u.z : 0u, on ? u.w : 0u};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                w[j][2 * i] = __builtin_bit_cast(float, q[i] << 16);
-                w[j][2 * i + 1] = __builtin_bit_cast(float, q[i] & 0xffff0000u);
-            }
-        } else {
-            const float* wp = reinterpret_cast<const float*>(W) + off;
-            const f32x4 w0 = *reinterpret_cast<const f32x4*>(wp);
-            const f32x4 w1 = *reinterpret_cast<const f32x4*>(wp + 4);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                w[j][i] = on ? w0[i] : 0.f;
-                w[j][4 + i] = on ? w1[i] : 0.f;
-            }
-        }
-    }
-}
-
 // [B][K] fp32 activations -> LDS.  The activations were written by other workgroups in this
 // launch, so EVERY load of them is an agent-scope relaxed 8-byte load (global_load_dwordx2 sc1:
 // bypasses this CU's L1, served coherently; Guideline 16 table row 1), 16 in flight per
@@ -122,52 +94,6 @@ __device__ __forceinline__ void stage(float* xs, const float* X, int n2) {
 __device__ __forceinline__ void publish(float* p, float v) {
     __hip_atomic_store(reinterpret_cast<unsigned*>(p), __builtin_bit_cast(unsigned, v),
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// One wave's row dot products for all batch rows, reduced so that lane `writer` of group b
-// holds acc[0] = sum_k X[b][k] w[k] (v4's reduce-scatter).  Returns acc[0].
-template <int MB, int NJ>
-__device__ __forceinline__ float row_dot(const float (&w)[NJ][8], const float* xs, int B, int K,
-                                         int lane) {
-    const int nch = K >> 3;
-    float acc[MB];
-#pragma unroll
-    for (int b = 0; b < MB; ++b) acc[b] = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int c = lane + 64 * j;
-        const int cc = c < nch ? c : 0;
-#pragma unroll
-        for (int b = 0; b < MB; ++b) {
-            const int bb = b < B ? b : 0;
-            const f32x4 x0 = *reinterpret_cast<const f32x4*>(xs + bb * K + cc * 8);
-            const f32x4 x1 = *reinterpret_cast<const f32x4*>(xs + bb * K + cc * 8 + 4);
-            float t = acc[b];
-            t = fmaf(w[j][0], x0[0], t); t = fmaf(w[j][1], x0[1], t);
-            t = fmaf(w[j][2], x0[2], t); t = fmaf(w[j][3], x0[3], t);
-            t = fmaf(w[j][4], x1[0], t); t = fmaf(w[j][5], x1[1], t);
-            t = fmaf(w[j][6], x1[2], t); t = fmaf(w[j][7], x1[3], t);
-            acc[b] = t;
-        }
-    }
-#pragma unroll
-    for (int lv = 0; lv < 6; ++lv) {
-        const int o = 32 >> lv;
-        const int n = MB >> lv;
-        const bool upper = (lane & o) != 0;
-        if (n > 1) {
-            const int half = n >> 1;
-#pragma unroll
-            for (int i = 0; i < half; ++i) {
-                const float send = upper ? acc[i] : acc[i + half];
-                const float keep = upper ? acc[i + half] : acc[i];
-                acc[i] = keep + xor_lane(send, o, lane);
-            }
-        } else {
-            acc[0] += xor_lane(acc[0], o, lane);
-        }
-    }
-    return acc[0];
 }
 
 // Grid barrier (MI355X guide, Guideline 16 table row 1): every wave drains its sc1 stores,

@@ -1,5 +1,7 @@
-"""Same-process A/B of decoder schedule variants (cdna guide §5.4 rule 24): interleaved
-rounds, median + min per variant.  Usage: python scripts/ab_decoder.py [B] [N] [rounds]"""
+"""Same-process A/B of the split decoder across dtypes and sizes (cdna guide §5.4 rule 24):
+interleaved rounds, median + min per variant.  Usage: python scripts/ab_decoder.py [B] [N] [rounds]
+AB_DTYPES=bf16,fp16 picks the dtypes; AB_VARIANTS names the runs interleaved per dtype (all run the
+one split-layout kernel: more than one name measures the run-to-run spread)."""
 import os
 import statistics
 import sys
@@ -13,9 +15,7 @@ from ldm_sdf import ops  # noqa: E402
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 R = int(sys.argv[3]) if len(sys.argv) > 3 else 5
-# variants: "s" = split layout (default kernel), "s<V>" (V = 1..3) = split with kernel variant
-# FV = V (LDM_FS_V, needs the `make DEV=1` library: csrc/decoder_fs.hip)
-VARIANTS = os.environ.get("AB_VARIANTS", "s,s2").split(",")
+VARIANTS = os.environ.get("AB_VARIANTS", "s").split(",")
 LAYOUT = {v: "split" for v in VARIANTS}
 FLOPS = 3146752
 dev = torch.device("cuda", 0)
@@ -29,8 +29,6 @@ for dtype in os.environ.get("AB_DTYPES", "bf16").split(","):
     times = {v: [] for v in VARIANTS}
     for r in range(R + 1):
         for v in VARIANTS:
-            if v.startswith("s") and v != "s16":
-                os.environ["LDM_FS_V"] = v[1:] or "0"
             e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
             e0.record()
             ops.decoder_grid_fwd(pks[v]["desc"], beta, N, 0, N, out=out)

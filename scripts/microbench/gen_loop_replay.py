@@ -11,7 +11,7 @@ python gen_loop_replay.py <dfs.dis> > loop_replay.hip && hipcc --offload-arch=gf
 import re
 import sys
 
-KERN = "dec_fs_kernelIDF16bLi256ELb0ELi2E"
+KERN = "dec_fs_kernelIDF16bLi256ELb0EE"
 
 
 def loops(dis):

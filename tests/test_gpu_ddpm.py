@@ -493,6 +493,67 @@ def test_sampling_bf16_1000_steps_b8_vs_oracle_rounded(dev, den, path):
     assert loose <= 5e-2, loose
 
 
+# ---- the per-step GEMV away from D = 256 / H = 1024 ----------------------------------------
+# (D, H) -> batches.  K = 1032: 4 chunks per lane, one live lane in chunk 2, none in chunk 3;
+# K = 520: 2 chunks, one live lane in chunk 1; K = 8: a single live lane; K = 2048: 4 chunks,
+# every lane live, with M = 8.  B = 8 | 9 straddle the 8- and 16-sample kernels; 15 (H = 1032)
+# and 8 (D = 2048) are the largest the 64 KiB LDS check admits.
+_GEMV_SHAPES = {(8, 1032): (1, 8, 9, 15), (8, 520): (1, 8, 9, 15), (2048, 8): (1, 8)}
+_gemv_nets = {}
+
+
+def _gemv_net(D, H):
+    """(model, fp64 oracle parameters) of a one-block network, built once per shape."""
+    from ldm_sdf import MLPDenoiser
+    from oracle import ref_cpu as R
+    if (D, H) not in _gemv_nets:
+        p = R.make_denoiser_params(D, H, n_blocks=1, TE=64, seed=7)
+        params = {n: getattr(p, n) for n in ("Wt1", "bt1", "Wt2", "bt2", "Win", "bin", "Wout",
+                                             "bout")}
+        params["Wblk0"], params["bblk0"] = p.Wblk[0], p.bblk[0]
+        _gemv_nets[(D, H)] = MLPDenoiser(D, H, n_blocks=1, TE=64, params=params), p
+    return _gemv_nets[(D, H)]
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("D,H,B", [(D, H, B) for (D, H), Bs in _GEMV_SHAPES.items() for B in Bs])
+def test_per_step_gemv_shapes_vs_oracle(dev, D, H, B, dtype):
+    """ldm_denoiser_fwd_uniform_t (t = 999) and ldm_sample_step (t = 999 and the no-noise t = 0)
+    at the chunk counts and partial chunks the D = 256 / H = 1024 tests never reach, against
+    the fp64 oracle (for bf16: on the bf16-rounded weight matrices, biases unrounded) within
+    test_denoiser_forward_vs_golden's bound 1e-4 max(1, max|want|).  The oracle's own fp32 run
+    is 0.2-1.3e-6 from fp64 on these inputs (max|want| 1.7-5.2): two orders of margin over any
+    summation order."""
+    from ldm_sdf import DDPMSchedule, ops
+    from oracle import ref_cpu as R
+    model, p = _gemv_net(D, H)
+    ref = p if dtype == "fp32" else _bf16_rounded_params(p)
+    desc = model.device_pack(dtype, dev)["desc"]
+    sch = DDPMSchedule()            # owns the device tables the descriptor points at
+    sdesc = sch.device(dev)["desc"]
+    tab = R.ddpm_tables()
+    emb = torch.from_numpy(R.timestep_embedding_table(1000, 64)).double()
+    g = torch.Generator().manual_seed(1000 * D + B)
+    x, z = torch.randn(B, D, generator=g), torch.randn(B, D, generator=g)
+    x_d, z_d = x.to(dev), z.to(dev)
+    ws = torch.empty(2 * B * H, device=dev)
+
+    def check(what, got, want):
+        err = float((got.cpu().double() - want).abs().max())
+        bound = 1e-4 * max(1.0, float(want.abs().max()))
+        print(f"gemv D={D} H={H} B={B} {dtype} {what}: max|want| {float(want.abs().max()):.3f} "
+              f"err {err:.3e} bound {bound:.3e}")
+        assert err < bound, (what, err, bound)
+
+    for t in (999, 0):
+        eps = R.denoiser_forward(ref, x.double(), torch.full((B,), t), emb)
+        if t == 999:
+            check("fwd t=999", ops.denoiser_fwd_uniform_t(desc, x_d, t), eps)
+        out = torch.empty_like(x_d)
+        ops.sample_step(desc, sdesc, x_d, z_d, t, out, ws)
+        check(f"step t={t}", out, R.ddpm_step(tab, x.double(), eps, z.double(), t))
+
+
 def test_sample_loop_timeout_surfaces_and_falls_back(dev, den, loop_form):
     """A persistent-loop barrier that gives up must not hand back partial latents silently:
     with a 1-poll spin limit the loop reports status 1, Sampler.run warns, re-runs the sample
