@@ -155,6 +155,45 @@ int ldm_decoder_points_fwd(const ldm_decoder_t* w, const float* beta, const floa
                            int B, int P, float* out, void* ws, size_t ws_bytes,
                            ldm_stream_t s);
 
+/* ---- narrow-band decode: only the 8^3 bricks that can hold the level set ---
+ * Brick: 8 x 8 x 8 voxels of the dense N^3 grid; nb = ceil(N / 8) per axis; brick (bz, by, bx)
+ *   covers the voxels [8b, min(8b + 8, N)) per axis; id = (bz nb + by) nb + bx; global id =
+ *   shape nb^3 + id.
+ * Lattice: per axis the nb + 1 fine-grid indices min(8b, N - 1), b = 0..nb -- a subset of the
+ *   fine grid with rule A1 coordinates, so a lattice value equals the dense decode's value at
+ *   that voxel bit for bit.  A brick's 8 corners are the lattice points b and b + 1 per axis
+ *   (when N - 1 is a multiple of 8 the last brick is one voxel thick and the two coincide).
+ * Active: min over the corners of |v - level| <= band, or the corners not all on one side of
+ *   level (v > level against v <= level), or a corner not finite.  band = L * 4 sqrt(3) * vs
+ *   (half a brick's diagonal) makes every brick the surface of an L-Lipschitz field touches
+ *   active; for any other field it is the caller's knob.  band = INFINITY: every brick.
+ * Fill: every voxel of an inactive brick gets the brick's corner-0 value, lattice (bz, by, bx).
+ * Sequence: ldm_band_lattice_coords -> ldm_decoder_points_fwd (coarse [B][(nb+1)^3]) ->
+ *   ldm_band_classify -> ldm_band_fill -> ldm_decoder_bricks_fwd; the volume then equals the
+ *   dense ldm_decoder_grid_fwd bit for bit on every voxel of an active brick.  Everything runs
+ *   on the caller's stream; the count stays on the device. */
+/* Scan scratch of ldm_band_classify (0 for invalid B / N). */
+size_t ldm_band_workspace_bytes(int B, int N);
+/* xyz_out fp32 [(nb+1)^3][3], z slowest: the lattice's coordinates. */
+int ldm_band_lattice_coords(int N, float vs, float origin, float* xyz_out, ldm_stream_t s);
+/* coarse fp32 [B][(nb+1)^3] -> active u8 [B nb^3] (16-byte aligned), bricks int32 [B nb^3]
+ * capacity: the active global ids in ascending order (a pure function of the input: block sums +
+ * scan, no atomics), count int32 [1] on the device.  B nb^3 < 2^31; band >= 0;
+ * ws 256-byte aligned, ldm_band_workspace_bytes(B, N). */
+int ldm_band_classify(const float* coarse, int B, int N, float level, float band,
+                      uint8_t* active, int32_t* bricks, int32_t* count, void* ws,
+                      size_t ws_bytes, ldm_stream_t s);
+/* A1+A3 brick mode: decodes the voxels of the first *count bricks of the list into the dense
+ * out fp32 [B][N][N][N] (ragged bricks clipped at N; entries outside [0, B nb^3) are skipped);
+ * other voxels are not written.  *count is read on the device (0 is valid).  4 B nb^3 < 2^31
+ * (fp32 descriptors: B nb^3 < 2^20).  ws as ldm_decoder_grid_fwd. */
+int ldm_decoder_bricks_fwd(const ldm_decoder_t* w, const float* beta, int B, int N, float vs,
+                           float origin, const int32_t* bricks, const int32_t* count, float* out,
+                           void* ws, size_t ws_bytes, ldm_stream_t s);
+/* Writes the fill into every inactive brick of out fp32 [B][N][N][N] (16-byte aligned). */
+int ldm_band_fill(const float* coarse, const uint8_t* active, int B, int N, float* out,
+                  ldm_stream_t s);
+
 /* ---- DDPM: A8 reverse step, A9 q_sample + eps-MSE ------------------------------------ */
 /* x_out[i] = c1[t]*(x[i] - c2[t]*eps[i]) + sigma[t]*z[i]  (z ignored at t == 0). n elements. */
 int ldm_ddpm_step(const ldm_sched_t* sc, const float* x, const float* eps, const float* z,

@@ -105,20 +105,50 @@ struct F32Args {
     float b_last;
     int npts, tiles_per_shape, N, k0, sw;
     float vs, origin;
+    const int32_t* bricks;   // bricks mode: ascending global brick ids, *count of them valid
+    const int32_t* count;
+    int nb, nbt;             // bricks per axis, B * nb^3
 };
 
-__global__ __launch_bounds__(256) void dec_f32_kernel_impl(F32Args a, int points) {
+// mode: DecMode.  Bricks mode: block b is tile b & 15 (32 points) of brick list[b >> 4]; point p
+// of the tile is brick-local index 32 (b & 15) + p (dx = idx & 7, dy = idx >> 3 & 7,
+// dz = idx >> 6), its voxel clamped to N - 1 for the coordinates and stored only inside the grid.
+// A block past the device count returns before its first barrier.
+__global__ __launch_bounds__(256) void dec_f32_kernel_impl(F32Args a, int mode) {
     __shared__ float hs[512 * 32];
     __shared__ float pxyz[32 * 3];
     const int t = threadIdx.x;
-    const int shape = blockIdx.x / a.tiles_per_shape;
-    const int local = blockIdx.x - shape * a.tiles_per_shape;
-    const int p0 = local * 32;
+    int shape, p0 = 0, vi = 0, vj = 0, vk = 0;
+    bool listed = true;
+    if (mode == kModeBricks) {
+        if ((int)(blockIdx.x >> 4) >= min(max(a.count[0], 0), a.nbt)) return;
+        const int raw = a.bricks[blockIdx.x >> 4];
+        LDM_DASSERT(raw >= 0 && raw < a.nbt);
+        listed = raw >= 0 && raw < a.nbt;
+        const int gid = min(max(raw, 0), a.nbt - 1);
+        const int nb2 = a.nb * a.nb, nb3 = nb2 * a.nb;
+        shape = gid / nb3;
+        const int id = gid - shape * nb3;
+        const int bz = id / nb2, r = id - bz * nb2;
+        const int by = r / a.nb;
+        const int idx = 32 * (int)(blockIdx.x & 15) + (t & 31);
+        vi = 8 * (r - by * a.nb) + (idx & 7);
+        vj = 8 * by + ((idx >> 3) & 7);
+        vk = 8 * bz + (idx >> 6);
+    } else {
+        shape = blockIdx.x / a.tiles_per_shape;
+        p0 = (blockIdx.x - shape * a.tiles_per_shape) * 32;
+    }
     if (t < 32) {
         int pt = p0 + t;
         if (pt >= a.npts) pt = a.npts - 1;
         float x, y, z;
-        if (points) {
+        if (mode == kModeBricks) {
+            const int m = a.N - 1;
+            x = grid_axis(min(vi, m), a.vs, a.origin);
+            y = grid_axis(min(vj, m), a.vs, a.origin);
+            z = grid_axis(min(vk, m), a.vs, a.origin);
+        } else if (mode == kModePoints) {
             const float* q = a.xyz + ((size_t)shape * a.npts + pt) * 3;
             x = q[0]; y = q[1]; z = q[2];
         } else {
@@ -202,7 +232,12 @@ __global__ __launch_bounds__(256) void dec_f32_kernel_impl(F32Args a, int points
         float s = 0.f;
         for (int f = 0; f < 512; ++f) s = fmaf(a.w_last[f], hs[f * 32 + t], s);
         const int pt = p0 + t;
-        if (pt < a.npts) a.out[(size_t)shape * a.npts + pt] = tanhf(s + a.b_last);
+        if (mode == kModeBricks) {
+            if (listed && vi < a.N && vj < a.N && vk < a.N)
+                a.out[(((size_t)shape * a.N + vk) * a.N + vj) * a.N + vi] = tanhf(s + a.b_last);
+        } else if (pt < a.npts) {
+            a.out[(size_t)shape * a.npts + pt] = tanhf(s + a.b_last);
+        }
     }
 }
 
@@ -249,13 +284,14 @@ int check_decoder(const ldm_decoder_t* w) {
 
 int decoder_fwd(const ldm_decoder_t* w, const float* beta, const float* xyz, int B, int npts,
                 int N, int k0, float vs, float origin, float* out, void* ws, size_t ws_bytes,
-                hipStream_t s) {
+                hipStream_t s, const int32_t* bricks = nullptr, const int32_t* count = nullptr,
+                int n_bricks = 0) {
     if (int e = check_decoder(w)) return e;
     LDM_REQUIRE(B >= 1 && npts >= 1, LDM_EINVAL, "empty decode (B=%d, npts=%d)", B, npts);
     LDM_REQUIRE((long long)B * npts < (1ll << 31), LDM_EINVAL, "B*npts too large");
     LDM_REQUIRE(beta && out, LDM_EINVAL, "beta/out NULL");
     LDM_REQUIRE(LDM_ALIGNED(beta, 16) && LDM_ALIGNED(out, 4), LDM_EALIGN, "misaligned buffers");
-    const bool points = xyz != nullptr;
+    const int mode = bricks ? kModeBricks : xyz ? kModePoints : kModeGrid;
     if (w->dtype == LDM_F32) {
         F32Args a;
         a.blob = (const float*)w->weights;
@@ -272,12 +308,22 @@ int decoder_fwd(const ldm_decoder_t* w, const float* beta, const float* xyz, int
         a.sw = w->skip_width;
         a.vs = vs;
         a.origin = origin;
-        hipLaunchKernelGGL(dec_f32_kernel_impl, dim3(B * a.tiles_per_shape), dim3(256), 0, s, a,
-                           points ? 1 : 0);
+        a.bricks = bricks;
+        a.count = count;
+        a.nb = (N + 7) / 8;
+        a.nbt = n_bricks;
+        unsigned grid = (unsigned)(B * a.tiles_per_shape);
+        if (mode == kModeBricks) {
+            // 16 tiles of 32 points per brick; a launch holds fewer than 2^32 threads
+            LDM_REQUIRE(n_bricks < (1 << 20), LDM_EINVAL,
+                        "fp32 brick decode: B * nb^3 = %d needs 2^20 bricks or fewer", n_bricks);
+            grid = 16u * (unsigned)n_bricks;
+        }
+        hipLaunchKernelGGL(dec_f32_kernel_impl, dim3(grid), dim3(256), 0, s, a, mode);
         return launch_status("ldm_decoder_fwd(f32)");
     }
     return decoder_fs_fwd(w, beta, xyz, B, npts, N, k0, vs, origin, out, ws, ws_bytes, s,
-                          num_cus());
+                          num_cus(), bricks, count, n_bricks);
 }
 
 }  // namespace
@@ -336,4 +382,23 @@ extern "C" int ldm_decoder_points_fwd(const ldm_decoder_t* w, const float* beta,
                                       ldm_stream_t s) {
     LDM_REQUIRE(xyz != nullptr && LDM_ALIGNED(xyz, 4), LDM_EINVAL, "xyz NULL");
     return decoder_fwd(w, beta, xyz, B, P, 0, 0, 0.f, 0.f, out, ws, ws_bytes, (hipStream_t)s);
+}
+
+extern "C" int ldm_decoder_bricks_fwd(const ldm_decoder_t* w, const float* beta, int B, int N,
+                                      float vs, float origin, const int32_t* bricks,
+                                      const int32_t* count, float* out, void* ws,
+                                      size_t ws_bytes, ldm_stream_t s) {
+    LDM_REQUIRE(N >= 2, LDM_EINVAL, "ldm_decoder_bricks_fwd: N = %d < 2", N);
+    LDM_REQUIRE(B >= 1, LDM_EINVAL, "ldm_decoder_bricks_fwd: B = %d < 1", B);
+    LDM_REQUIRE(bricks && count, LDM_EINVAL, "ldm_decoder_bricks_fwd: bricks/count NULL");
+    LDM_REQUIRE(LDM_ALIGNED(bricks, 4) && LDM_ALIGNED(count, 4), LDM_EALIGN,
+                "ldm_decoder_bricks_fwd: misaligned bricks/count");
+    // a tile index is 4 * brick + quarter: 4 B nb^3 must fit 31 bits
+    const long long nb = (N + 7) / 8;
+    LDM_REQUIRE(nb * nb * nb <= (long long)0x1fffffff / B, LDM_EINVAL,
+                "ldm_decoder_bricks_fwd: 4 * B * nb^3 = 4 * %d * %lld^3 does not fit 31 bits", B,
+                nb);
+    // npts = 1: the dense [B][N][N][N] output is addressed by voxel, not by point index
+    return decoder_fwd(w, beta, nullptr, B, 1, N, 0, vs, origin, out, ws, ws_bytes,
+                       (hipStream_t)s, bricks, count, (int)(B * nb * nb * nb));
 }

@@ -7,6 +7,10 @@
 namespace ldm {
 namespace dec {
 
+// Where a decoder tile's points come from: a run of the dense grid (rule A1 in the kernel), a
+// point list, or a quarter of a listed 8^3 brick of the dense grid (band.hip).
+enum DecMode { kModeGrid = 0, kModePoints = 1, kModeBricks = 2 };
+
 #define LDM_STR2(x) #x
 #define LDM_STR(x) LDM_STR2(x)
 

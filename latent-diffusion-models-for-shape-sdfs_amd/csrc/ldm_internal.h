@@ -104,7 +104,8 @@ size_t decoder_fs_aux_bytes(int B);
 int decoder_fs_n_stages(int skip_width);
 int decoder_fs_fwd(const ldm_decoder_t* w, const float* beta, const float* xyz, int B, int npts,
                    int N, int k0, float vs, float origin, float* out, void* ws, size_t ws_bytes,
-                   hipStream_t s, int num_cus);
+                   hipStream_t s, int num_cus, const int32_t* bricks = nullptr,
+                   const int32_t* count = nullptr, int n_bricks = 0);
 
 // matrix-core path of ldm_linear (linear_mfma.hip)
 int linear_mfma(const ldm_linear_args_t& a, hipStream_t s);

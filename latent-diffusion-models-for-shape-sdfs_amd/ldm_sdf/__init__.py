@@ -10,6 +10,8 @@ from .unet import UNet1DDenoiser  # noqa: F401
 from .mesh import marching_cubes, marching_cubes_batch, mc_table, write_ply  # noqa: F401
 from .api import (Sampler, TrainState, decode, decode_points, resolve_decode_dtype,  # noqa: F401
                   sample, train, train_step)
+from .band import (BandInfo, decode_band, extract_mesh, lattice_indices,  # noqa: F401
+                   n_bricks)
 from .autodecoder import (AutoDecoderState, autodecoder_train_step,  # noqa: F401
                           train_autodecoder)
 from . import ops, dist, pack, data  # noqa: F401

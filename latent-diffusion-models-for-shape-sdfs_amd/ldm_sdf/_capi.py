@@ -145,6 +145,12 @@ SIGNATURES = [
     ("ldm_decoder_grid_fwd", _i, [C.POINTER(Decoder), _fp, _i, _i, _i, _i, _f, _f, _fp, _vp,
                                   _sz, _vp]),
     ("ldm_decoder_points_fwd", _i, [C.POINTER(Decoder), _fp, _fp, _i, _i, _fp, _vp, _sz, _vp]),
+    ("ldm_band_workspace_bytes", _sz, [_i, _i]),
+    ("ldm_band_lattice_coords", _i, [_i, _f, _f, _fp, _vp]),
+    ("ldm_band_classify", _i, [_fp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    ("ldm_decoder_bricks_fwd", _i, [C.POINTER(Decoder), _fp, _i, _i, _f, _f, _vp, _vp, _fp, _vp,
+                                    _sz, _vp]),
+    ("ldm_band_fill", _i, [_fp, _vp, _i, _i, _fp, _vp]),
     ("ldm_ddpm_step", _i, [C.POINTER(Sched), _fp, _fp, _fp, _i, _i, _fp, _vp]),
     ("ldm_q_sample", _i, [C.POINTER(Sched), _fp, _fp, _vp, _i, _i, _fp, _vp]),
     ("ldm_eps_mse_loss", _i, [_fp, _fp, _i, _fp, _fp, _vp]),

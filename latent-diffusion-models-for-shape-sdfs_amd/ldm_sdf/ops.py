@@ -114,6 +114,90 @@ def decoder_points_fwd(desc: capi.Decoder, beta: torch.Tensor, xyz: torch.Tensor
     return out
 
 
+# ------------------------------------------------------------------------- narrow-band decode
+def _nb(N: int) -> int:
+    return (int(N) + 7) // 8
+
+
+def band_lattice_coords(N: int, bbox=(-1.0, 1.0), device=None) -> torch.Tensor:
+    """Coordinates ``[(nb+1)^3, 3]`` of the brick lattice (fine-grid indices ``min(8b, N-1)``)."""
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    n1 = _nb(N) + 1
+    out = torch.empty(n1 ** 3, 3, device=device, dtype=torch.float32)
+    capi.check(capi.load().ldm_band_lattice_coords(int(N), voxel_size(N, bbox), float(bbox[0]),
+                                                   out.data_ptr(), capi.stream_handle(device)),
+               "ldm_band_lattice_coords")
+    return out
+
+
+def band_classify(coarse: torch.Tensor, N: int, level: float, band: float,
+                  ws: Optional[torch.Tensor] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """coarse ``[B, (nb+1)^3]`` (any shape with that many elements per shape) -> ``active`` u8
+    ``[B*nb^3]``, ``bricks`` int32 ``[B*nb^3]`` (the first ``count`` entries: the active global
+    ids, ascending) and ``count`` int32 ``[1]``, all on the device (no read-back)."""
+    capi.require_device(coarse)
+    _f32(coarse)
+    _contig(coarse)
+    B, nb = coarse.shape[0], _nb(N)
+    if coarse.numel() != B * (nb + 1) ** 3:
+        raise capi.LdmError("band_classify: coarse must hold [B, (nb+1)^3] values")
+    dev = coarse.device
+    active = torch.empty(B * nb ** 3, device=dev, dtype=torch.uint8)
+    bricks = torch.empty(B * nb ** 3, device=dev, dtype=torch.int32)
+    count = torch.empty(1, device=dev, dtype=torch.int32)
+    lib = capi.load()
+    need = lib.ldm_band_workspace_bytes(B, int(N))
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 256), device=dev, dtype=torch.uint8)
+    capi.check(lib.ldm_band_classify(coarse.data_ptr(), B, int(N), float(level), float(band),
+                                     active.data_ptr(), bricks.data_ptr(), count.data_ptr(),
+                                     ws.data_ptr(), ws.numel(), capi.stream_handle(dev)),
+               "ldm_band_classify")
+    return active, bricks, count
+
+
+def band_fill(coarse: torch.Tensor, active: torch.Tensor, N: int, out: torch.Tensor) -> torch.Tensor:
+    """The fill (corner-0 value) into every inactive brick of the dense ``out [B, N, N, N]``."""
+    capi.require_device(coarse, active, out)
+    _f32(coarse, out)
+    _contig(coarse, active, out)
+    B = coarse.shape[0]
+    if out.numel() != B * N ** 3 or active.numel() != B * _nb(N) ** 3 or \
+            active.dtype != torch.uint8:
+        raise capi.LdmError("band_fill: out must be [B, N, N, N], active uint8 [B*nb^3]")
+    capi.check(capi.load().ldm_band_fill(coarse.data_ptr(), active.data_ptr(), B, int(N),
+                                         out.data_ptr(), capi.stream_handle(out.device)),
+               "ldm_band_fill")
+    return out
+
+
+def decoder_bricks_fwd(desc: capi.Decoder, beta: torch.Tensor, N: int, bricks: torch.Tensor,
+                       count: torch.Tensor, out: torch.Tensor, bbox=(-1.0, 1.0),
+                       ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Decode the voxels of the first ``count`` listed bricks into the dense ``out [B, N, N, N]``
+    (``count`` is read on the device)."""
+    capi.require_device(beta, bricks, count, out)
+    _f32(out)
+    _contig(beta, bricks, count, out)
+    B = beta.shape[0]
+    if out.numel() != B * N ** 3 or bricks.dtype != torch.int32 or count.dtype != torch.int32 \
+            or bricks.numel() < B * _nb(N) ** 3:
+        raise capi.LdmError("decoder_bricks_fwd: out must be [B, N, N, N], bricks int32 "
+                            "[B*nb^3], count int32 [1]")
+    lib = capi.load()
+    wsb = lib.ldm_workspace_bytes_layout(capi.LDM_OP_DECODER_GRID, B, int(N), desc.dtype,
+                                         desc.layout)
+    if ws is None or ws.numel() < wsb:
+        ws = torch.empty(max(wsb, 16), device=beta.device, dtype=torch.uint8)
+    capi.check(lib.ldm_decoder_bricks_fwd(C.byref(desc), beta.data_ptr(), B, int(N),
+                                          voxel_size(N, bbox), float(bbox[0]), bricks.data_ptr(),
+                                          count.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), capi.stream_handle(beta.device)),
+               "ldm_decoder_bricks_fwd")
+    return out
+
+
 # ---------------------------------------------------------------------------------------- A8/A9
 def ddpm_step(sched_desc: capi.Sched, x: torch.Tensor, eps: torch.Tensor,
               z: Optional[torch.Tensor], t: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
