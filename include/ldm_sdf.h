@@ -194,6 +194,49 @@ int ldm_decoder_bricks_fwd(const ldm_decoder_t* w, const float* beta, int B, int
 int ldm_band_fill(const float* coarse, const uint8_t* active, int B, int N, float* out,
                   ldm_stream_t s);
 
+/* ---- decoder input gradients with frozen weights (csrc/decoder_grad.hip) ----
+ * The derivative of the decoder's output with respect to its input [z || xyz]: SDF normals
+ * (d f / d xyz) and the latent gradient of a frozen decoder (d / d z through the folded biases:
+ * ldm_decoder_fold -> ldm_decoder_points_grad -> ldm_decoder_fold_bwd).  16-bit operands
+ * (LDM_F16 / LDM_BF16), fp32 accumulation; forward and backward of a 64-point tile run in one
+ * launch and keep only the ReLU sign bits.  Layers 1..7 are given twice, row-major [out][in] and
+ * transposed [in][out], in `dtype`, zero padded to 256 rows / columns where the skip width is
+ * 253: w[l] is [M_l][K_l], wt[l] is [K_l][M_l] with M_3 = K_4 = 256 or 512 (K_4: the h columns
+ * of layer 4 only) and every other dimension 512. */
+typedef struct ldm_decoder_grad {
+    int32_t abi_version;  /* must equal LDM_ABI_VERSION */
+    int32_t dtype;        /* LDM_F16 or LDM_BF16 (LDM_F32: LDM_ENOSYS) */
+    int32_t skip_width;   /* 253 or 512 */
+    int32_t latent_dim;   /* L */
+    const void* w[8];     /* w[1..7] (w[0] unused), 16-byte aligned */
+    const void* wt[8];    /* wt[1..7] (wt[0] unused), 16-byte aligned */
+    const float* bias;    /* fp32 [8][512]: b_l zero padded; rows 0 and 4 unused (beta) */
+    const float* wxyz;    /* fp32 [2][512][3]  xyz columns of layer 0 and layer 4 */
+    const float* wz;      /* fp32 [2][512][L]  latent columns of layer 0 and layer 4 */
+    const float* w_last;  /* fp32 [512] final 512->1 weights, natural order */
+    float b_last;         /* final bias */
+} ldm_decoder_grad_t;
+/* Workspace of ldm_decoder_points_grad: the per-tile partial sums (0 for invalid sizes). */
+size_t ldm_decoder_grad_ws_bytes(int B, int P, int dtype);
+/* beta fp32 [B][2][512] (ldm_decoder_fold), xyz fp32 [B][P][3] ->
+ *   sdf_out   fp32 [B][P]       tanh(pre)
+ *   dxyz_out  fp32 [B][P][3]    s_p d pre_p / d xyz_p                          (nullable)
+ *   dbeta_out fp32 [B][2][512]  sum_p s_p d pre_p / d beta, a fixed-order sum  (nullable)
+ * gt == NULL, gradient mode: s_p = 1 - f_p^2, so the outputs are derivatives of f = tanh(pre);
+ *   delta and scale are ignored and loss_out must be NULL.
+ * gt fp32 [B][P], loss mode: s_p = d loss_p / d pre_p of ldm_sdf_l1_loss's clamped-L1 term
+ *   (delta > 0, scale); loss_out[0] (nullable) = scale * sum_p |clamp(f_p) - clamp(gt_p)|.
+ * The backward itself always carries d pre / d (.), s_p multiplies the fp32 outputs only.
+ * B <= 65535, B P < 2^31; ws 256-byte aligned.  Deterministic: no atomics. */
+int ldm_decoder_points_grad(const ldm_decoder_grad_t* w, const float* beta, const float* xyz,
+                            int B, int P, const float* gt, float delta, float scale,
+                            float* sdf_out, float* dxyz_out, float* dbeta_out, float* loss_out,
+                            void* ws, size_t ws_bytes, ldm_stream_t s);
+/* The transposed fold: dz_out fp32 [B][L] = wz[0]^T dbeta[b][0] + wz[1]^T dbeta[b][1], summed in
+ * fp64 and rounded once. */
+int ldm_decoder_fold_bwd(const ldm_decoder_grad_t* w, const float* dbeta, int B, float* dz_out,
+                         ldm_stream_t s);
+
 /* ---- DDPM: A8 reverse step, A9 q_sample + eps-MSE ------------------------------------ */
 /* x_out[i] = c1[t]*(x[i] - c2[t]*eps[i]) + sigma[t]*z[i]  (z ignored at t == 0). n elements. */
 int ldm_ddpm_step(const ldm_sched_t* sc, const float* x, const float* eps, const float* z,

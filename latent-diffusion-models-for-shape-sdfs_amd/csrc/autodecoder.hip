@@ -5,9 +5,11 @@
 //
 //   relu_bwd_kernel        g = dy * (y > 0) on the post-activation
 //   sdf_l1_kernel          pred = tanh(pre); clamped L1 vs the ground-truth SDF and its
-//                          gradient w.r.t. pre (one workgroup, fixed summation order)
+//                          gradient w.r.t. pre (one workgroup, fixed summation order; the
+//                          per-element term is sdf_loss.h, shared with decoder_grad.hip)
 //   latent_reg_kernel      DeepSDF code_reg: coef * sum_s |z_s|, gradient coef * z_s / |z_s|
 #include "ldm_internal.h"
+#include "sdf_loss.h"
 
 #include <math.h>
 
@@ -29,20 +31,6 @@ __device__ __forceinline__ void block_sum_1024(float* red, float s) {
         if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
     }
-}
-
-__device__ __forceinline__ float clampd(float x, float d) { return fminf(fmaxf(x, -d), d); }
-
-// Per element: loss term and d/d pre.  Written out (no fast-math intrinsics) so the tanh
-// matches the C library's within an ulp or two.
-__device__ __forceinline__ float sdf_l1_term(float pre, float gt, float delta, float scale,
-                                             float& grad) {
-    const float pred = tanhf(pre);
-    const float diff = clampd(pred, delta) - clampd(gt, delta);
-    const float sg = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-    const bool pass = pred >= -delta && pred <= delta;
-    grad = pass ? scale * sg * (1.f - pred * pred) : 0.f;
-    return fabsf(diff);
 }
 
 // One workgroup; U groups of loads in flight per thread (clamped index, predicated use).

@@ -7,13 +7,15 @@ over ``torch.distributed`` (RCCL).
 """
 from .models import DDPMSchedule, MLPDenoiser, SDFDecoder, decoder_layer_dims  # noqa: F401
 from .unet import UNet1DDenoiser  # noqa: F401
-from .mesh import marching_cubes, marching_cubes_batch, mc_table, write_ply  # noqa: F401
+from .mesh import (marching_cubes, marching_cubes_batch, mc_table, vertex_normals,  # noqa: F401
+                   write_ply)
 from .api import (Sampler, TrainState, decode, decode_points, resolve_decode_dtype,  # noqa: F401
                   sample, train, train_step)
 from .band import (BandInfo, decode_band, extract_mesh, lattice_indices,  # noqa: F401
                    n_bricks)
 from .autodecoder import (AutoDecoderState, autodecoder_train_step,  # noqa: F401
                           train_autodecoder)
+from .grad import fit_latents, sdf_grad  # noqa: F401
 from . import ops, dist, pack, data  # noqa: F401
 from ._capi import LdmError, load as load_library  # noqa: F401
 

@@ -42,6 +42,13 @@ class Decoder(C.Structure):
                 ("b_last", C.c_float), ("layout", C.c_int32)]
 
 
+class DecoderGrad(C.Structure):
+    """ldm_decoder_grad_t: the frozen-decoder gradient kernel's weights (csrc/decoder_grad.hip)."""
+    _fields_ = [("abi_version", C.c_int32), ("dtype", C.c_int32), ("skip_width", C.c_int32),
+                ("latent_dim", C.c_int32), ("w", _vp * 8), ("wt", _vp * 8), ("bias", _vp),
+                ("wxyz", _vp), ("wz", _vp), ("w_last", _vp), ("b_last", C.c_float)]
+
+
 class Sched(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("T", C.c_int32), ("sqrt_ab", _vp),
                 ("sqrt_1mab", _vp), ("c1", _vp), ("c2", _vp), ("sigma", _vp)]
@@ -151,6 +158,10 @@ SIGNATURES = [
     ("ldm_decoder_bricks_fwd", _i, [C.POINTER(Decoder), _fp, _i, _i, _f, _f, _vp, _vp, _fp, _vp,
                                     _sz, _vp]),
     ("ldm_band_fill", _i, [_fp, _vp, _i, _i, _fp, _vp]),
+    ("ldm_decoder_grad_ws_bytes", _sz, [_i, _i, _i]),
+    ("ldm_decoder_points_grad", _i, [C.POINTER(DecoderGrad), _fp, _fp, _i, _i, _fp, _f, _f, _fp,
+                                     _fp, _fp, _fp, _vp, _sz, _vp]),
+    ("ldm_decoder_fold_bwd", _i, [C.POINTER(DecoderGrad), _fp, _i, _fp, _vp]),
     ("ldm_ddpm_step", _i, [C.POINTER(Sched), _fp, _fp, _fp, _i, _i, _fp, _vp]),
     ("ldm_q_sample", _i, [C.POINTER(Sched), _fp, _fp, _vp, _i, _i, _fp, _vp]),
     ("ldm_eps_mse_loss", _i, [_fp, _fp, _i, _fp, _fp, _vp]),

@@ -27,7 +27,7 @@ import torch
 from . import _capi as capi
 from . import ops
 from .api import resolve_decode_dtype
-from .mesh import marching_cubes
+from .mesh import marching_cubes, vertex_normals
 from .models import SDFDecoder
 
 BRICK = 8
@@ -104,11 +104,17 @@ def decode_band(decoder: SDFDecoder, latents: torch.Tensor, resolution: int, *,
                          active.view(B, nb, nb, nb).bool(), bricks, count, band)
 
 
-def extract_mesh(decoder: SDFDecoder, latents: torch.Tensor, resolution: int, **kw
-                 ) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+def extract_mesh(decoder: SDFDecoder, latents: torch.Tensor, resolution: int, *,
+                 normals: bool = False, **kw) -> List[Tuple[torch.Tensor, ...]]:
     """``decode_band`` then ``marching_cubes`` per shape at the same ``level`` and ``bbox``:
-    a list of ``(verts, faces)``.  Keyword arguments are ``decode_band``'s."""
+    a list of ``(verts, faces)``, or with ``normals`` of ``(verts, faces, normals)`` -- the
+    field's unit gradient at every vertex (``mesh.vertex_normals``, fp16).  The other keyword
+    arguments are ``decode_band``'s."""
     kw.pop("return_info", None)
     level, bbox = kw.get("level", 0.0), kw.get("bbox", (-1.0, 1.0))
     vol = decode_band(decoder, latents, resolution, **kw)
-    return [marching_cubes(vol[b], level, bbox) for b in range(vol.shape[0])]
+    meshes = [marching_cubes(vol[b], level, bbox) for b in range(vol.shape[0])]
+    if not normals:
+        return meshes
+    lat = latents if latents.dim() > 1 else latents[None]
+    return [(v, f, vertex_normals(decoder, lat[b], v)) for b, (v, f) in enumerate(meshes)]

@@ -68,11 +68,31 @@ def marching_cubes_batch(volumes: torch.Tensor, level: float = 0.0, bbox=(-1.0, 
             for b in range(rank, volumes.shape[0], world)]
 
 
+def vertex_normals(decoder, latent: torch.Tensor, verts: torch.Tensor, *,
+                   dtype: str = "fp16") -> torch.Tensor:
+    """Unit normals ``[V, 3]`` of the decoder's level set at ``verts [V, 3]``: the field's own
+    gradient ``grad f / |grad f|`` (``sdf_grad``), the zero vector where the gradient vanishes.
+    They point toward larger values, the side ``marching_cubes``' winding faces.  ``latent`` is
+    one shape's code ``[L]`` (or ``[1, L]``)."""
+    from .grad import sdf_grad
+    capi.require_device(latent, verts)
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError("vertex_normals: verts must be [V, 3]")
+    if verts.shape[0] == 0:
+        return torch.zeros(0, 3, device=verts.device, dtype=torch.float32)
+    _, g = sdf_grad(decoder, latent.reshape(1, -1), verts[None], dtype=dtype)
+    g = g[0]
+    n = g.norm(dim=1, keepdim=True)
+    return torch.where(n > 0, g / n.clamp_min(torch.finfo(torch.float32).tiny),
+                       torch.zeros_like(g))
+
+
 def write_ply(path: str, verts, faces, offset: Optional[Sequence[float]] = None,
-              scale: Optional[float] = None) -> None:
+              scale: Optional[float] = None, normals=None) -> None:
     """Binary little-endian PLY (vertex float x, y, z; face ``list uchar int``), as DeepSDF's
     ``convert_sdf_samples_to_ply`` writes it; ``offset``/``scale`` undo a normalisation
-    (``p / scale - offset``) when given."""
+    (``p / scale - offset``) when given.  ``normals [V, 3]`` adds the vertex properties
+    ``nx ny nz``; without it the file is what it always was."""
     v = verts.detach().cpu().numpy() if isinstance(verts, torch.Tensor) else np.asarray(verts)
     f = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
     v = v.astype("<f4")
@@ -80,8 +100,16 @@ def write_ply(path: str, verts, faces, offset: Optional[Sequence[float]] = None,
         v = v / np.float32(scale)
     if offset is not None:
         v = v - np.asarray(offset, np.float32)
+    props = "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        nrm = (normals.detach().cpu().numpy() if isinstance(normals, torch.Tensor)
+               else np.asarray(normals)).astype("<f4")
+        if nrm.shape != v.shape:
+            raise ValueError(f"write_ply: normals {nrm.shape} do not match verts {v.shape}")
+        v = np.concatenate([v.reshape(-1, 3), nrm.reshape(-1, 3)], axis=1)
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
     head = ("ply\nformat binary_little_endian 1.0\n"
-            f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+            f"element vertex {len(v)}\n{props}"
             f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
     rec = np.zeros(len(f), dtype=[("n", "u1"), ("v", "<i4", (3,))])
     rec["n"] = 3

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _capi as capi
-from .pack import pack_decoder
+from .pack import pack_decoder, pack_decoder_grad
 
 # ----------------------------------------------------------------------------------------
 # decoder
@@ -71,6 +71,7 @@ class SDFDecoder:
         self.weights = [w.detach().to("cpu", torch.float32).contiguous() for w in weights]
         self.biases = [b.detach().to("cpu", torch.float32).contiguous() for b in biases]
         self._dev: Dict[Tuple[str, torch.device, str], Dict[str, object]] = {}
+        self._dev_grad: Dict[Tuple[str, torch.device], Dict[str, object]] = {}
 
     @property
     def skip_width(self) -> int:
@@ -87,6 +88,44 @@ class SDFDecoder:
     def invalidate(self) -> None:
         """Call after the weights changed (auto-decoder training): drops the packed copies."""
         self._dev.clear()
+        self._dev_grad.clear()
+
+    def device_pack_grad(self, dtype: str, device: torch.device) -> Dict[str, object]:
+        """Packed device arrays + ``ldm_decoder_grad_t`` of the frozen-decoder gradient kernel
+        (csrc/decoder_grad.hip), cached per dtype/device; ``dtype`` is "fp16" or "bf16"."""
+        device = torch.device(device)
+        key = (dtype, device)
+        if key not in self._dev_grad:
+            if dtype not in ("fp16", "bf16"):
+                raise capi.LdmError(f"the decoder gradient kernel runs in fp16 or bf16, not "
+                                    f"{dtype!r} (there is no fp32 gradient kernel)")
+            if not self.gpu_supported():
+                raise capi.LdmError("GPU decoder kernels support DeepSDF 8x512 with skip at 4")
+            host = pack_decoder_grad(self.weights, self.biases, self.latent_dim, dtype)
+            dev: Dict[str, object] = {}
+            for k, v in host.items():
+                if isinstance(v, torch.Tensor):
+                    dev[k] = v.to(device)
+                elif isinstance(v, list):
+                    dev[k] = [None if t is None else t.to(device) for t in v]
+                else:
+                    dev[k] = v
+            desc = capi.DecoderGrad()
+            desc.abi_version = capi.ABI_VERSION
+            desc.dtype = capi.DTYPE_CODES[dtype]
+            desc.skip_width = host["skip_width"]
+            desc.latent_dim = self.latent_dim
+            for l in range(1, 8):
+                desc.w[l] = dev["w"][l].data_ptr()
+                desc.wt[l] = dev["wt"][l].data_ptr()
+            desc.bias = dev["bias"].data_ptr()
+            desc.wxyz = dev["wxyz"].data_ptr()
+            desc.wz = dev["wz"].data_ptr()
+            desc.w_last = dev["w_last"].data_ptr()
+            desc.b_last = host["b_last"]
+            dev["desc"] = desc
+            self._dev_grad[key] = dev
+        return self._dev_grad[key]
 
     def device_pack(self, dtype: str, device: torch.device,
                     layout: Optional[str] = None) -> Dict[str, object]:

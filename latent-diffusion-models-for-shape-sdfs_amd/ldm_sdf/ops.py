@@ -114,6 +114,72 @@ def decoder_points_fwd(desc: capi.Decoder, beta: torch.Tensor, xyz: torch.Tensor
     return out
 
 
+# ------------------------------------------------------- decoder input gradients (frozen weights)
+GRAD_TILE = 64      # points per tile of csrc/decoder_grad.hip
+
+
+def decoder_grad_ws_bytes(B: int, P: int, dtype_code: int) -> int:
+    return int(capi.load().ldm_decoder_grad_ws_bytes(int(B), int(P), int(dtype_code)))
+
+
+def decoder_points_grad(desc: capi.DecoderGrad, beta: torch.Tensor, xyz: torch.Tensor, *,
+                        gt: Optional[torch.Tensor] = None, delta: float = 0.0,
+                        scale: float = 0.0, want_dxyz: bool = True, want_dbeta: bool = False,
+                        want_loss: bool = False, ws: Optional[torch.Tensor] = None
+                        ) -> Dict[str, torch.Tensor]:
+    """``ldm_decoder_points_grad``: beta ``[B, 2, 512]``, xyz ``[B, P, 3]`` -> a dict with
+    ``sdf [B, P]`` and, as asked, ``dxyz [B, P, 3]``, ``dbeta [B, 2, 512]``, ``loss [1]``.
+    ``gt [B, P]`` selects loss mode (``delta``, ``scale``); without it the outputs are the
+    derivatives of tanh(pre)."""
+    capi.require_device(beta, xyz, gt)
+    _f32(beta, xyz, gt)
+    _contig(beta, xyz, gt)
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or tuple(beta.shape) != (xyz.shape[0], 2, 512):
+        raise capi.LdmError("decoder_points_grad: xyz must be [B, P, 3] and beta [B, 2, 512]")
+    B, P = xyz.shape[0], xyz.shape[1]
+    if gt is not None and tuple(gt.shape) != (B, P):
+        raise capi.LdmError("decoder_points_grad: gt must be [B, P]")
+    if want_loss and gt is None:
+        raise capi.LdmError("decoder_points_grad: the loss needs gt")
+    dev = xyz.device
+    out = {"sdf": torch.empty(B, P, device=dev, dtype=torch.float32)}
+    if want_dxyz:
+        out["dxyz"] = torch.empty(B, P, 3, device=dev, dtype=torch.float32)
+    if want_dbeta:
+        out["dbeta"] = torch.empty(B, 2, 512, device=dev, dtype=torch.float32)
+    if want_loss:
+        out["loss"] = torch.empty(1, device=dev, dtype=torch.float32)
+    lib = capi.load()
+    need = lib.ldm_decoder_grad_ws_bytes(B, P, desc.dtype)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 256), device=dev, dtype=torch.uint8)
+    capi.check(lib.ldm_decoder_points_grad(
+        C.byref(desc), beta.data_ptr(), xyz.data_ptr(), B, P, capi.ptr(gt), float(delta),
+        float(scale), out["sdf"].data_ptr(), capi.ptr(out.get("dxyz")),
+        capi.ptr(out.get("dbeta")), capi.ptr(out.get("loss")), ws.data_ptr(), ws.numel(),
+        capi.stream_handle(dev)), "ldm_decoder_points_grad")
+    return out
+
+
+def decoder_fold_bwd(desc: capi.DecoderGrad, dbeta: torch.Tensor,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``ldm_decoder_fold_bwd``: dbeta ``[B, 2, 512]`` -> dz ``[B, L]``."""
+    capi.require_device(dbeta, out)
+    _f32(dbeta, out)
+    _contig(dbeta, out)
+    B = dbeta.shape[0]
+    if tuple(dbeta.shape) != (B, 2, 512):
+        raise capi.LdmError("decoder_fold_bwd: dbeta must be [B, 2, 512]")
+    if out is None:
+        out = torch.empty(B, desc.latent_dim, device=dbeta.device, dtype=torch.float32)
+    if tuple(out.shape) != (B, desc.latent_dim):
+        raise capi.LdmError("decoder_fold_bwd: out must be [B, L]")
+    capi.check(capi.load().ldm_decoder_fold_bwd(C.byref(desc), dbeta.data_ptr(), B,
+                                                out.data_ptr(), capi.stream_handle(dbeta.device)),
+               "ldm_decoder_fold_bwd")
+    return out
+
+
 # ------------------------------------------------------------------------- narrow-band decode
 def _nb(N: int) -> int:
     return (int(N) + 7) // 8

@@ -235,3 +235,37 @@ def pack_decoder(weights, biases, latent_dim: int, dtype: str,
     else:
         raise ValueError(f"unknown decoder dtype {dtype!r}")
     return out
+
+
+def pack_decoder_grad(weights, biases, latent_dim: int, dtype: str) -> Dict[str, object]:
+    """Host-side arrays of an ``ldm_decoder_grad_t`` (csrc/decoder_grad.hip) for ``dtype`` in
+    {bf16, fp16}: layers 1..7 row-major ``[out][in]`` (``w``) and transposed (``wt``) in the
+    16-bit type, zero padded to 256 where the skip width is 253 (layer 3's rows, the h columns of
+    layer 4 -- its latent and xyz columns are ``wz`` / ``wxyz``); fp32 biases ``[8][512]`` (rows 0
+    and 4 stay zero: those layers' biases are folded into beta), ``wxyz``, ``wz``, the final
+    weights in natural order and the final bias."""
+    if dtype not in ("bf16", "fp16"):
+        raise ValueError(f"the gradient kernel takes bf16 or fp16 weights, not {dtype!r}")
+    dt = torch.bfloat16 if dtype == "bf16" else torch.float16
+    pieces = canonical_pieces(weights, biases, latent_dim)
+    sw = pieces["skip_width"]
+    S = skip_pad(sw)
+    w, wt = [None], [None]
+    bias = torch.zeros(8, H, dtype=torch.float64)
+    for l in range(1, 8):
+        m = pieces["main"][l]
+        wp = torch.zeros(S if l == 3 else H, S if l == 4 else H, dtype=torch.float64)
+        wp[:m.shape[0], :m.shape[1]] = m
+        wp = _round(wp, dt)
+        w.append(wp.contiguous())
+        wt.append(wp.T.contiguous())
+        if l != 4:
+            bias[l, :m.shape[0]] = pieces["bias"][l]
+    return {
+        "skip_width": sw, "latent_dim": latent_dim, "w": w, "wt": wt,
+        "bias": bias.to(torch.float32).contiguous(),
+        "wxyz": pieces["wxyz"].to(torch.float32).contiguous(),
+        "wz": pieces["wz"].to(torch.float32).contiguous(),
+        "w_last": pieces["w_last"].to(torch.float32).contiguous(),
+        "b_last": float(pieces["b_last"]),
+    }
