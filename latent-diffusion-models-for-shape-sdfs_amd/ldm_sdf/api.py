@@ -612,12 +612,7 @@ def train(denoiser: MLPDenoiser, schedule: DDPMSchedule, latents: torch.Tensor, 
         denoiser.invalidate_tables()
     elif state.optimizer is None:
         denoiser.invalidate()    # fp32 training updated the masters only: bf16 packs are stale
-    # one device->host transfer for the whole run, not one per step
-    pend = [i for i, l in enumerate(state.losses) if isinstance(l, torch.Tensor)]
-    if pend:
-        vals = torch.cat([state.losses[i].reshape(1).float() for i in pend]).tolist()
-        for i, v in zip(pend, vals):
-            state.losses[i] = v
+    ops.read_back_losses(state.losses)
     return state
 
 

@@ -5,30 +5,36 @@ SDF samples, producing the latents that the diffusion model is then trained on a
 decoder that decodes them.  Objective: ``oracle/ref_autodecoder.py`` (DeepSDF's clamped L1 on
 ``tanh`` outputs plus the per-sample latent L2 regulariser; no dropout).
 
-Every FLOP runs in ``libldm_sdf.so``:
+Every FLOP runs in ``libldm_sdf.so``; torch provides memory, the copies that build the padded
+operands and Adam (plumbing), as in ``api.train``.  ``autodecoder_train_step`` has two paths:
 
-* the 9 forward linears are ``ldm_linear`` with the ReLU epilogue;
-* the backward products are ``ldm_linear`` on transposed views (``G W``, ``G^T X``);
-* the bias gradients are ``ldm_colsum``, the per-shape latent gradients ``ldm_colsum_segments``;
-* the loss and its gradient are ``ldm_sdf_l1_loss``, the code regulariser ``ldm_latent_l2_reg``.
+* ``dtype="bf16"`` (the default, and the one ``bench.py`` measures), ``_train_step_gemm_bf16``:
+  every product is an ``ldm_gemm_bf16`` problem.  Each activation ``h_l`` and gradient ``g_l``
+  is kept once, in bf16, in both layouts: [Np, w] (the A operand of the next product, the ReLU
+  mask of the G W products) and k-blocked [w, Np] (the B operand of the weight gradients, whose
+  sum runs over the samples).  The epilogues write both (``Cb`` / ``CbT``), apply ReLU or its
+  backward (``relu_bwd`` on the saved post-activation) and emit the 32-row column sums that
+  become the bias gradients; the weight gradients are split-K, one slice per sample block.
+* ``dtype="fp32"``, ``_train_step_linear_fp32``: exact fp32 products on ``ldm_linear`` (forward
+  with the ReLU epilogue, ``G W`` with ``LDM_EPI_MASK_R``, ``G^T X`` on transposed views),
+  ``ldm_colsum`` for the biases and ``ldm_colsum_segments`` for the per-shape latent gradients.
 
-torch provides memory, the row gather's destination copies and Adam (plumbing), as in
-``api.train``.
+Both share the loss (``ldm_sdf_l1_loss``), the code regulariser (``ldm_latent_l2_reg``) and ONE
+padded working layout, ``_Layout``: ``work_weights`` rebuilds it from the fp32 masters each
+step, ``master_grads`` cuts the gradients back out of it.  The paths differ in its numbers only:
 
-Working layout (rebuilt from the fp32 masters each step, in the GEMM dtype).  It pads so that
-every operand row is a multiple of 16 bytes and the matrix-core path can use vector loads:
-
-* ``Zx`` [N, 264] = ``[z_s || xyz || 0]`` (8-column multiple: 16-byte rows in bf16). It is the
-  input of layer 0 and the second segment of layer 4.
-* The backward's ``G W`` products apply the ReLU mask in their epilogue (``LDM_EPI_MASK_R``
-  with the saved post-activation), so ``relu_bwd`` is a separate pass nowhere.
-* Layer ``skip-1`` (253 outputs) is padded to 256 rows with zero weights and biases, so its
-  ReLU output ``h3`` [N, 256] has 3 zero columns. Layer ``skip`` is two segments,
-  ``h3 · W4h^T + Zx · W4z^T``.
-* The master gradients are cut back out of the padded ones.
+* ``Zx`` = ``[z_s || xyz || 0]`` (the input of layer 0, the second segment of layer ``skip``) is
+  ``zw`` columns wide: L + 3 rounded up to 8 in fp32 (264; 16-byte rows in bf16 too), to a GEMM
+  K segment of 64 in bf16 (320).
+* Layer ``skip - 1`` (``hs`` = 253 outputs) is padded to ``hsp`` rows with zero weights and
+  biases (a multiple of 4 in fp32, of 64 in bf16: 256 either way), so its ReLU output has zero
+  columns past ``hs``.  Layer ``skip`` is two segments, ``h3 · W4h^T + Zx · W4z^T``.
+* bf16 also pads the N = S P samples to ``Np`` rows (a multiple of ``_KQ``; rows >= N zero),
+  cut into ``nblk`` blocks of ``KT``: the K slices of the weight gradients.
 """
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
@@ -46,6 +52,15 @@ __all__ = ["AutoDecoderState", "autodecoder_train_step", "train_autodecoder", "C
 CLAMP_DIST = 0.1          # DeepSDF ClampingDistance
 CODE_REG_LAMBDA = 1e-4    # DeepSDF CodeRegularizationLambda
 
+_KQ = 128          # row padding of the sample axis (the K of the weight-gradient products)
+# ldm_gemm_bf16 tile of the weight-gradient products (128 x 128: each slice walks KT = 8192
+# samples, long enough for the bigger tile's per-CU operand economy); tuning runs pass
+# ``wgrad_tile`` to autodecoder_train_step (the product reads no environment variable).
+# Round 6 sweep (scripts/ad_wgrad_ab.py, profiles/r06am): the persistent 128 x 128 tile on a
+# 2-deep ring (17) 30.9-31.1 ms/step, 14 31.0, the earlier 3 31.3-31.9, others 32-34; same bits
+WGRAD_TILE = 17
+_KSEG = 64         # bf16 padding of [z || xyz] and of the skip width (a GEMM K segment)
+
 
 def _check_decoder(dec: SDFDecoder) -> Tuple[int, int]:
     if dec.widen_skip or dec.n_hidden != 8 or dec.skip != 4:
@@ -54,62 +69,91 @@ def _check_decoder(dec: SDFDecoder) -> Tuple[int, int]:
     return dec.latent_dim, dec.hidden
 
 
-def _zx_width(L: int) -> int:
-    """[z || xyz] padded to a multiple of 8 columns: 16-byte rows in bf16 as well as fp32."""
-    return (L + 3 + 7) // 8 * 8
+def _round_up(n: int, m: int) -> int:
+    return -(-n // m) * m
 
 
-def _pad_rows(n: int) -> int:
-    return (n + 3) // 4 * 4
+@dataclass(frozen=True)
+class _Layout:
+    """The padded working layout of one step (module doc): every size its stages share."""
+    L: int
+    H: int
+    skip: int
+    S: int
+    P: int
+    dtype: torch.dtype    # of the working weights
+    row_pad: int          # hs (the skip width) is padded to a multiple of this: hsp
+    col_pad: int          # L + 3 ([z || xyz]) to a multiple of this: zw
+    hs: int
+    hsp: int
+    zw: int
+    N: int                # S * P samples, padded to Np rows = nblk blocks of KT
+    Np: int
+    nblk: int
+    KT: int
+
+
+def _layout(L: int, H: int, skip: int, hs: int, S: int, P: int, dtype: torch.dtype) -> _Layout:
+    N = S * P
+    if dtype == torch.bfloat16:
+        row_pad = col_pad = _KSEG
+        Np = _round_up(N, _KQ)
+        KT = next(kt for kt in (8192, 4096, 2048, 1024, 512, 256, 128) if Np % kt == 0)
+        nblk = Np // KT
+    else:
+        row_pad, col_pad, Np, KT, nblk = 4, 8, N, N, 1
+    return _Layout(L=L, H=H, skip=skip, S=S, P=P, dtype=dtype, row_pad=row_pad, col_pad=col_pad,
+                   hs=hs, hsp=_round_up(hs, row_pad), zw=_round_up(L + 3, col_pad),
+                   N=N, Np=Np, nblk=nblk, KT=KT)
+
+
+def _zero_padded(src: torch.Tensor, shape, dtype: torch.dtype) -> torch.Tensor:
+    out = torch.zeros(shape, device=src.device, dtype=dtype)
+    out[tuple(slice(n) for n in src.shape)] = src
+    return out
 
 
 def work_weights(masters: Dict[str, torch.Tensor], L: int, H: int, skip: int,
-                 dtype: torch.dtype) -> Dict[str, torch.Tensor]:
-    """Padded working copies (see module doc) of the fp32 masters ``W{l}``/``b{l}``.  Pure
-    data movement; also used on CPU tensors by the host-logic tests."""
-    zw = _zx_width(L)
+                 dtype: torch.dtype, row_pad: int = 4, col_pad: int = 8
+                 ) -> Dict[str, torch.Tensor]:
+    """Padded working copies (see module doc) of the fp32 masters ``W{l}``/``b{l}``: ``W{l}``
+    in ``dtype`` with the skip layer as ``W4h`` / ``W4z``, and layer ``skip - 1``'s padded fp32
+    bias ``b{skip-1}p``.  The defaults are the fp32 path's pads.  Pure data movement; also used
+    on CPU tensors by the host-logic tests."""
+    zw = _round_up(L + 3, col_pad)
     hs = masters[f"W{skip - 1}"].shape[0]             # skip width, 253 for L=256, H=512
-    hsp = _pad_rows(hs)
-    dev = masters["W0"].device
-    w: Dict[str, torch.Tensor] = {}
-    W0 = torch.zeros(H, zw, device=dev, dtype=dtype)
-    W0[:, :L + 3] = masters["W0"]
-    w["W0"] = W0
-    for l in range(1, 9):
-        if l == skip - 1:
-            Wp = torch.zeros(hsp, H, device=dev, dtype=dtype)
-            Wp[:hs] = masters[f"W{l}"]
-            bp = torch.zeros(hsp, device=dev, dtype=torch.float32)
-            bp[:hs] = masters[f"b{l}"]
-            w[f"W{l}"], w[f"b{l}p"] = Wp, bp
-        elif l == skip:
-            Ws = masters[f"W{l}"]
-            Wh = torch.zeros(H, hsp, device=dev, dtype=dtype)
-            Wh[:, :hs] = Ws[:, :hs]
-            Wz = torch.zeros(H, zw, device=dev, dtype=dtype)
-            Wz[:, :L + 3] = Ws[:, hs:]
-            w["W4h"], w["W4z"] = Wh, Wz
-        else:
-            w[f"W{l}"] = masters[f"W{l}"].to(dtype)
+    hsp = _round_up(hs, row_pad)
+    Ws = masters[f"W{skip}"]
+    w = {f"W{l}": masters[f"W{l}"].to(dtype) for l in range(1, 9) if l not in (skip - 1, skip)}
+    w["W0"] = _zero_padded(masters["W0"], (H, zw), dtype)
+    w[f"W{skip - 1}"] = _zero_padded(masters[f"W{skip - 1}"], (hsp, H), dtype)
+    w[f"b{skip - 1}p"] = _zero_padded(masters[f"b{skip - 1}"], (hsp,), torch.float32)
+    w["W4h"] = _zero_padded(Ws[:, :hs], (H, hsp), dtype)
+    w["W4z"] = _zero_padded(Ws[:, hs:], (H, zw), dtype)
     return w
+
+
+def _working(masters: Dict[str, torch.Tensor], lay: _Layout):
+    """(weights, biases) of a step in layout ``lay``: ``work_weights`` and the fp32 biases
+    ``b{l}``, layer ``skip - 1``'s being the padded one."""
+    w = work_weights(masters, lay.L, lay.H, lay.skip, lay.dtype, lay.row_pad, lay.col_pad)
+    b = {f"b{l}": masters[f"b{l}"].contiguous() for l in range(9)}
+    b[f"b{lay.skip - 1}"] = w.pop(f"b{lay.skip - 1}p")
+    return w, b
 
 
 def master_grads(gw: Dict[str, torch.Tensor], L: int, skip: int, hs: int,
                  out: Dict[str, torch.Tensor]) -> None:
-    """Cut the padded working gradients back to the master shapes (into ``out``)."""
-    out["W0"].copy_(gw["W0"][:, :L + 3])
-    out["b0"].copy_(gw["b0"])
-    for l in range(1, 9):
-        if l == skip - 1:
-            out[f"W{l}"].copy_(gw[f"W{l}"][:hs])
-            out[f"b{l}"].copy_(gw[f"b{l}"][:hs])
-        elif l == skip:
-            out[f"W{l}"][:, :hs].copy_(gw["W4h"][:, :hs])
-            out[f"W{l}"][:, hs:].copy_(gw["W4z"][:, :L + 3])
-            out[f"b{l}"].copy_(gw[f"b{l}"])
+    """Cut the padded working gradients (``W{l}`` with ``W4h`` / ``W4z`` at the skip, ``b{l}``)
+    back to the master shapes (into ``out``)."""
+    for l in range(9):
+        Wm, bm = out[f"W{l}"], out[f"b{l}"]
+        bm.copy_(gw[f"b{l}"][:bm.shape[0]])
+        if l == skip:
+            Wm[:, :hs].copy_(gw["W4h"][:, :hs])
+            Wm[:, hs:].copy_(gw["W4z"][:, :L + 3])
         else:
-            out[f"W{l}"].copy_(gw[f"W{l}"])
-            out[f"b{l}"].copy_(gw[f"b{l}"])
+            Wm.copy_(gw[f"W{l}"][:Wm.shape[0], :Wm.shape[1]])
 
 
 def autodecoder_train_step(masters: Dict[str, torch.Tensor], z: torch.Tensor, xyz: torch.Tensor,
@@ -129,29 +173,42 @@ def autodecoder_train_step(masters: Dict[str, torch.Tensor], z: torch.Tensor, xy
     Returns (loss [1], weight grads keyed like ``masters``, latent grads [S, L]).
     """
     capi.require_device(z, xyz, sdf, masters["W0"])
-    L, H = latent_dim, hidden
+    L = latent_dim
     S, P = sdf.shape
-    N = S * P
     if tuple(z.shape) != (S, L) or tuple(xyz.shape) != (S, P, 3):
         raise capi.LdmError(f"autodecoder_train_step: z{tuple(z.shape)} xyz{tuple(xyz.shape)} "
                             f"sdf{tuple(sdf.shape)}")
+    if dtype not in ("bf16", "fp32"):
+        raise capi.LdmError(f"autodecoder_train_step: dtype 'bf16' or 'fp32', got {dtype!r}")
+    lay = _layout(L, hidden, skip, masters[f"W{skip - 1}"].shape[0], S, P,
+                  torch.bfloat16 if dtype == "bf16" else torch.float32)
+    z = z.contiguous()
     if dtype == "bf16":
-        return _train_step_gemm_bf16(masters, z, xyz, sdf, L=L, H=H, skip=skip, delta=delta,
-                                     reg_lambda=reg_lambda, epoch=epoch, grads=grads,
-                                     wgrad_tile=WGRAD_TILE if wgrad_tile is None else wgrad_tile)
+        loss, gw, gz = _train_step_gemm_bf16(
+            masters, z, xyz, sdf, lay, delta, WGRAD_TILE if wgrad_tile is None else wgrad_tile)
+    else:
+        loss, gw, gz = _train_step_linear_fp32(masters, z, xyz, sdf, lay, delta)
+    # both paths' tail: the code regulariser (added to loss and gz) and the cut-back
+    coef = reg_lambda * min(1.0, epoch / 100.0) / S
+    if coef != 0.0:
+        ops.latent_l2_reg(z, coef, loss, gz)
+    if grads is None:
+        grads = {k: torch.empty_like(v) for k, v in masters.items()}
+    master_grads(gw, L, skip, lay.hs, grads)
+    return loss, grads, gz
+
+
+def _train_step_linear_fp32(masters, z, xyz, sdf, lay: _Layout, delta):
+    """Exact fp32 step on ``ldm_linear`` (module doc): (loss, padded weight
+    gradients, latent gradients) before the code regulariser."""
     dev = z.device
-    cp = capi.COMPUTE_CODES[dtype]
-    wdt = torch.bfloat16 if dtype == "bf16" else torch.float32
-    hs = masters[f"W{skip - 1}"].shape[0]
-    hsp, zw = _pad_rows(hs), _zx_width(L)
-    w = work_weights(masters, L, H, skip, wdt)
-    b = {f"b{l}": masters[f"b{l}"] for l in range(9)}
-    b[f"b{skip - 1}"] = w[f"b{skip - 1}p"]
+    cp = capi.COMPUTE_FP32
+    L, H, skip, S, N, hsp, zw = lay.L, lay.H, lay.skip, lay.S, lay.N, lay.hsp, lay.zw
+    w, b = _working(masters, lay)
     f32 = dict(device=dev, dtype=torch.float32)
 
     # ---- inputs: Zx = [z_s || xyz || 0] per sample
-    z = z.contiguous()
-    owner = torch.arange(S, device=dev, dtype=torch.int32).repeat_interleave(P)
+    owner = torch.arange(S, device=dev, dtype=torch.int32).repeat_interleave(lay.P)
     Zx = torch.zeros(N, zw, **f32)
     Zx[:, :L].copy_(ops.gather_rows(z, owner))
     Zx[:, L:L + 3].copy_(xyz.reshape(N, 3))
@@ -185,8 +242,7 @@ def autodecoder_train_step(masters: Dict[str, torch.Tensor], z: torch.Tensor, xy
             ops.linear(g.T, Zx.T, gw["W4z"], compute=cp)
             ops.linear(g, w["W4z"][:, :L].t().contiguous(), dz, compute=cp)   # latent part, layer 4
         else:
-            Wl = w[f"W{l}"]
-            gw[f"W{l}"] = torch.empty(Wl.shape[0], Wl.shape[1], **f32)
+            gw[f"W{l}"] = torch.empty(w[f"W{l}"].shape, **f32)
             ops.linear(g.T, xin.T, gw[f"W{l}"], compute=cp)
         gw[f"b{l}"] = torch.empty(g.shape[1], **f32)
         ops.colsum(g, gw[f"b{l}"])
@@ -203,23 +259,16 @@ def autodecoder_train_step(masters: Dict[str, torch.Tensor], z: torch.Tensor, xy
 
     gz = torch.empty(S, L, **f32)
     ops.colsum_segments(dz, S, gz)
-    coef = reg_lambda * min(1.0, epoch / 100.0) / S
-    if coef != 0.0:
-        ops.latent_l2_reg(z, coef, loss, gz)
-    if grads is None:
-        grads = {k: torch.empty_like(v) for k, v in masters.items()}
-    master_grads(gw, L, skip, hs, grads)
-    return loss, grads, gz
+    return loss, gw, gz
 
 
-_KQ = 128          # row padding of the sample axis (the K of the weight-gradient products)
-# ldm_gemm_bf16 tile of the weight-gradient products (128 x 128: each slice walks KT = 8192
-# samples, long enough for the bigger tile's per-CU operand economy); tuning runs pass
-# ``wgrad_tile`` to autodecoder_train_step (the product reads no environment variable).
-# Round 6 sweep (scripts/ad_wgrad_ab.py, profiles/r06am): the persistent 128 x 128 tile on a
-# 2-deep ring (17) 30.9-31.1 ms/step, 14 31.0, the earlier 3 31.3-31.9, others 32-34; same bits
-WGRAD_TILE = 17
-_KSEG = 64         # column padding of [z || xyz] (a GEMM K segment)
+def _owner_index(S: int, P: int, Np: int, dev) -> torch.Tensor:
+    """[Np] long: the shape that owns each padded sample row (shape-major: row m belongs to
+    shape m // P); the padding rows >= S P get S, one past the last shape."""
+    N = S * P
+    owner_pad = torch.full((Np,), S, device=dev, dtype=torch.long)
+    owner_pad[:N] = torch.arange(S, device=dev).repeat_interleave(P)
+    return owner_pad
 
 
 def _ad_inputs(z, xyz, S, P, Np, zw, KT, gather=False):
@@ -229,7 +278,9 @@ def _ad_inputs(z, xyz, S, P, Np, zw, KT, gather=False):
     shape: when P is a multiple of KT every block lies in one shape and both layouts are written
     by broadcast copies (round 6: the index gathers of [N, L] took ≈ 1 ms of the 64 x 16384
     step); else (or ``gather``) by the per-sample gathers.  Same values either way
-    (``tests/test_autodecoder_inputs.py``)."""
+    (``tests/test_autodecoder_inputs.py``).  Every sample-axis (transposed) operand of the step
+    is k-BLOCKED like ``ZxT``: a weight-gradient slice is one block, so the rows it streams lie
+    KT * 2 bytes apart instead of 2 MB apart (one page per row: 9 us per k-step, TLB-bound)."""
     L = z.shape[1]
     N = S * P
     nblk = Np // KT
@@ -242,8 +293,7 @@ def _ad_inputs(z, xyz, S, P, Np, zw, KT, gather=False):
         Zx[:N].view(S, P, zw)[:, :, :L] = zb[:, None, :]
         ZxT[:N // KT].view(S, P // KT, zw, KT)[:, :, :L, :] = zb[:, None, :, None]
     else:
-        owner_pad = torch.full((Np,), S, device=dev, dtype=torch.long)
-        owner_pad[:N] = torch.arange(S, device=dev).repeat_interleave(P)
+        owner_pad = _owner_index(S, P, Np, dev)
         Zx[:N, :L] = z[owner_pad[:N]]
         zT = torch.zeros(L, S + 1, **bf)          # column S: the padding rows' zero code
         zT[:, :S] = z.t()
@@ -255,203 +305,155 @@ def _ad_inputs(z, xyz, S, P, Np, zw, KT, gather=False):
     return Zx, ZxT
 
 
-def _train_step_gemm_bf16(masters, z, xyz, sdf, *, L, H, skip, delta, reg_lambda, epoch,
-                          grads, wgrad_tile=WGRAD_TILE):
-    """bf16 matrix-core step on ``ldm_gemm_bf16`` (include/ldm_sdf.h).
+def _train_step_gemm_bf16(masters, z, xyz, sdf, lay: _Layout, delta, wgrad_tile):
+    """bf16 matrix-core step on ``ldm_gemm_bf16`` (module doc; include/ldm_sdf.h; DESIGN.md
+    §11): (loss, padded weight gradients, latent gradients) before the code regulariser.
+    Numerics: operands rounded to bf16 (RNE), fp32 accumulation -- as ``ldm_linear``'s bf16."""
+    N = lay.N
+    w, WT, bias = _weights_bf16(masters, lay)
+    Zx, ZxT = _ad_inputs(z, xyz, lay.S, lay.P, lay.Np, lay.zw, lay.KT)
+    h, hT, pre = _forward_bf16(w, bias, Zx, lay)
+    loss, g8 = ops.sdf_l1_loss(pre[:N].reshape(N, 1), sdf.reshape(N, 1).contiguous(), delta,
+                               1.0 / N)
+    gw, gcs, Gs = _backward_bf16(WT, g8, h, hT, ZxT, lay, wgrad_tile)
+    _bias_sums_bf16(gcs, gw)
+    return loss, gw, _latent_grad_bf16(masters, gcs, Gs, lay)
 
-    Every activation is kept once in bf16, in both layouts: ``h_l`` [Np, w] (the A operand of
-    the next forward product and of the G W products' ReLU mask) and ``h_l^T`` [w, Np] (the B
-    operand of the weight gradients, whose sum runs over the samples).  The epilogues write
-    them (``Cb`` / ``CbT``), the ReLU backward rides in the G W products (``relu_bwd`` on the
-    saved bf16 post-activation), the bias gradients are the epilogues' 32-row column sums, and
-    the weight gradients are split-K products over the sample axis.  The latent gradient needs
-    no [N, L] product: per shape, ``sum_p g4 W4z + g0 W0`` = (per-shape column sums of g4 and
-    g0) x the latent columns, a [S, H] x [H, L] product in fp32.  Numerics: operands rounded to
-    bf16 (RNE), fp32 accumulation -- as the ``ldm_linear`` bf16 path."""
-    dev = z.device
-    S, P = sdf.shape
-    N = S * P
-    Np = -(-N // _KQ) * _KQ
-    hs = masters[f"W{skip - 1}"].shape[0]
-    hsp = -(-hs // 64) * 64                      # skip width padded to a GEMM K segment
-    zw = -(-(L + 3) // _KSEG) * _KSEG
-    bf = dict(device=dev, dtype=torch.bfloat16)
-    f32 = dict(device=dev, dtype=torch.float32)
 
-    # ---- working weights (bf16, padded) and their transposes for the G W products
-    W = {}
-    W0 = torch.zeros(H, zw, **bf)
-    W0[:, :L + 3] = masters["W0"]
-    W["W0"] = W0
-    for l in range(1, 8):
-        if l == skip - 1:
-            Wp = torch.zeros(hsp, H, **bf)
-            Wp[:hs] = masters[f"W{l}"]
-            W[f"W{l}"] = Wp
-        elif l == skip:
-            Ws = masters[f"W{l}"]
-            Wh = torch.zeros(H, hsp, **bf)
-            Wh[:, :hs] = Ws[:, :hs]
-            Wz = torch.zeros(H, zw, **bf)
-            Wz[:, :L + 3] = Ws[:, hs:]
-            W["W4h"], W["W4z"] = Wh, Wz
-        else:
-            W[f"W{l}"] = masters[f"W{l}"].to(torch.bfloat16)
-    WT = {k: v.t().contiguous() for k, v in W.items() if k != "W0"}
-    bias = {f"b{l}": masters[f"b{l}"].contiguous() for l in range(9)}
-    bp = torch.zeros(hsp, **f32)
-    bp[:hs] = masters[f"b{skip - 1}"]
-    bias[f"b{skip - 1}"] = bp
+def _weights_bf16(masters, lay: _Layout):
+    """(w, WT, bias): the bf16 working weights, their transposes for the G W products (none
+    for ``W0`` and ``W4z``: no gradient is taken through ``Zx``) and the fp32 biases."""
+    w, bias = _working(masters, lay)
+    WT = {k: v.t().contiguous() for k, v in w.items() if k not in ("W0", "W4z", "W8")}
     # the 512 -> 1 layer as a K = 64 product for its backward (g8 in column 0, zeros beside)
-    w8 = masters["W8"].reshape(-1)
-    W8T = torch.zeros(H, 64, **bf)
-    W8T[:, 0] = w8
-    W8 = w8.to(torch.bfloat16).reshape(1, H).contiguous()
+    WT["W8"] = torch.zeros(lay.H, _KSEG, device=w["W8"].device, dtype=torch.bfloat16)
+    WT["W8"][:, 0] = w["W8"].reshape(-1)
+    return w, WT, bias
 
-    # ---- inputs: Zx = [z_s || xyz || 0] per sample, rows >= N zero, both layouts.  The
-    # sample-axis (transposed) operands are k-BLOCKED, [nblk][width][KT]: a weight-gradient
-    # slice is one block, so the rows it streams lie KT * 2 bytes apart inside one block
-    # instead of 2 MB apart (one memory page per row: measured 9 us per k-step, TLB-bound).
-    KT = next(kt for kt in (8192, 4096, 2048, 1024, 512, 256, 128) if Np % kt == 0)
-    nblk = Np // KT
-    Zx, ZxT = _ad_inputs(z, xyz, S, P, Np, zw, KT)
 
-    # ---- forward: h_l = ReLU(...) in bf16, both layouts (rows >= N written as zeros)
+def _forward_bf16(w, bias, Zx, lay: _Layout):
+    """(h, hT, pre): ``h_l = ReLU(...)`` in bf16 in both layouts (rows >= N written as zeros),
+    l = 0..7, and the fp32 ``pre`` [Np, 1] of the last layer."""
+    N, Np, KT = lay.N, lay.Np, lay.KT
+    bf = dict(device=Zx.device, dtype=torch.bfloat16)
     h, hT = [], []
     x = Zx
     for l in range(8):
-        width = hsp if l == skip - 1 else H
+        width = lay.hsp if l == lay.skip - 1 else lay.H
         y = torch.empty(Np, width, **bf)
-        yT = torch.empty(nblk, width, KT, **bf)
-        segs = ([(x, W["W4h"]), (Zx, W["W4z"])] if l == skip else [(x, W[f"W{l}"])])
+        yT = torch.empty(lay.nblk, width, KT, **bf)
+        segs = ([(x, w["W4h"]), (Zx, w["W4z"])] if l == lay.skip else [(x, w[f"W{l}"])])
         ops.gemm([ops.gemm_problem(segs, Np, width, mode="relu", M_valid=N, bias=bias[f"b{l}"],
                                    Cb=y, CbT=yT, ct_blk=KT)])
         h.append(y)
         hT.append(yT)
         x = y
-    pre = torch.empty(Np, 1, **f32)
-    ops.gemm([ops.gemm_problem([(x, W8)], Np, 1, M_valid=N, bias=bias["b8"], C=pre)])
-    loss, g8 = ops.sdf_l1_loss(pre[:N].reshape(N, 1), sdf.reshape(N, 1).contiguous(), delta,
-                               1.0 / N)
+    pre = torch.empty(Np, 1, device=Zx.device, dtype=torch.float32)
+    ops.gemm([ops.gemm_problem([(x, w["W8"])], Np, 1, M_valid=N, bias=bias["b8"], C=pre)])
+    return h, hT, pre
 
-    # ---- backward
-    gw = {}
-    gb = {}
-    ws_cache = {}
 
-    def ws_for(n, slot):
-        # keyed by (size, slot in the launch's problem list): two problems of ONE launch must
-        # never share partial slabs, even when their sizes agree (e.g. S == zw on the one-hot
-        # path); launches run in stream order, so reuse across launches is safe
-        t = ws_cache.get((n, slot))
-        if t is None:
-            t = ws_cache[(n, slot)] = torch.empty(n, **f32)
-        return t
+def _wgrad(ws_cache, lay: _Layout, gT, xT, M_, N_, out, slot):
+    """The problem out [M_, N_] fp32 = sum over the samples of gT x xT^T; gT [nblk, M_, KT] and
+    xT [nblk, N_, KT] blocked: split-K with one slice per block.  `slot` = the problem's
+    index within its launch (its own split-K workspace, from the step's ``ws_cache``)."""
+    nblk, KT = lay.nblk, lay.KT
+    if nblk == 1:
+        return ops.gemm_problem([(gT[0], xT[0])], M_, N_, C=out)
+    # keyed by (size, slot in the launch's problem list): two problems of ONE launch must
+    # never share partial slabs, even when their sizes agree (e.g. S == zw on the one-hot
+    # path); launches run in stream order, so reuse across launches is safe
+    n = nblk * M_ * N_
+    ws = ws_cache.get((n, slot))
+    if ws is None:
+        ws = ws_cache[(n, slot)] = torch.empty(n, device=out.device, dtype=torch.float32)
+    return ops.gemm_problem([(gT[0], xT[0])], M_, N_, C=out, k_split=nblk, ws=ws,
+                            slices=(gT.shape[1] * KT, xT.shape[1] * KT))
 
-    def wgrad(gT, xT, M_, N_, out, slot):
-        """out [M_, N_] fp32 = sum over the samples of gT x xT^T; gT [nblk, M_, KT] and
-        xT [nblk, N_, KT] blocked: split-K with one slice per block.  `slot` = the problem's
-        index within its launch (its own split-K workspace)."""
-        if nblk == 1:
-            return ops.gemm_problem([(gT[0], xT[0])], M_, N_, C=out)
-        return ops.gemm_problem([(gT[0], xT[0])], M_, N_, C=out, k_split=nblk,
-                                ws=ws_for(nblk * M_ * N_, slot),
-                                slices=(gT.shape[1] * KT, xT.shape[1] * KT))
 
+def _gw_relu_bwd(g, WdT, R, lay: _Layout):
+    """(g_prev, g_prev^T, column sums): ``(g W) * [R > 0]`` for g [Np, wout] and W^T = WdT
+    [win, wout], in bf16 in both layouts, with the fp32 sums of each 32-row block."""
+    Np, KT, win = lay.Np, lay.KT, R.shape[1]
+    g_prev = torch.empty(Np, win, device=g.device, dtype=torch.bfloat16)
+    gT_prev = torch.empty(lay.nblk, win, KT, device=g.device, dtype=torch.bfloat16)
+    cs = torch.empty(-(-Np // 32), win, device=g.device, dtype=torch.float32)
+    ops.gemm([ops.gemm_problem([(g, WdT)], Np, win, mode="relu_bwd", M_valid=lay.N, Rb=R,
+                               Cb=g_prev, CbT=gT_prev, colsum=cs, ct_blk=KT)])
+    return g_prev, gT_prev, cs
+
+
+def _backward_bf16(WT, g8, h, hT, ZxT, lay: _Layout, wgrad_tile):
+    """(gw, gcs, Gs) from g8 = dL/d pre [N, 1]: the padded weight gradients (and ``b8``), the
+    32-row column sums of every g_l (bias / latent gradients), and on the one-hot path the
+    per-shape column sums of g_skip and g_0.  Layer 8 runs its G W product before its weight
+    gradient, the others after (the launch order the step has always had)."""
+    H, skip, S, N, Np, KT, nblk = lay.H, lay.skip, lay.S, lay.N, lay.Np, lay.KT, lay.nblk
+    dev = g8.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    wg = functools.partial(_wgrad, {}, lay)      # one workspace cache for the whole step
     # layer 8: dW8 = g8^T h7, db8 = sum g8; g7 = (g8 w8) * [h7 > 0]
-    g8b = torch.zeros(Np, 64, **bf)
+    g8b = torch.zeros(Np, _KSEG, device=dev, dtype=torch.bfloat16)
     g8b[:N, 0] = g8.reshape(N)
     g8row = g8b[:, 0].contiguous().reshape(nblk, 1, KT)      # blocked [nblk][1][KT]
-    gw["W8"] = torch.empty(1, H, **f32)
-    gb["b8"] = torch.empty(1, **f32)
-    ops.colsum(g8.reshape(N, 1), gb["b8"])
-    nrow32 = -(-Np // 32)
-    g_cur = torch.empty(Np, H, **bf)
-    gT_cur = torch.empty(nblk, H, KT, **bf)
-    cs = torch.empty(nrow32, H, **f32)
-    ops.gemm([ops.gemm_problem([(g8b, W8T)], Np, H, mode="relu_bwd", M_valid=N, Rb=h[7],
-                               Cb=g_cur, CbT=gT_cur, colsum=cs, ct_blk=KT)])
-    ops.gemm([wgrad(g8row, hT[7], 1, H, gw["W8"], 0)], tile=wgrad_tile)
-    colsums = {7: cs}
+    gw = {"W8": torch.empty(1, H, **f32), "b8": torch.empty(1, **f32)}
+    ops.colsum(g8.reshape(N, 1), gw["b8"])
     gcs = {}                                       # g_l per 32-row block sums (bias / latent)
+    g, gT, gcs[7] = _gw_relu_bwd(g8b, WT["W8"], h[7], lay)
+    ops.gemm([wg(g8row, hT[7], 1, H, gw["W8"], 0)], tile=wgrad_tile)
     Gs = {}                                        # per-shape column sums of g_skip and g_0
     onehot = None
-    if P % 32:                                     # 32-row blocks straddle shapes: a one-hot
+    if lay.P % 32:                                 # 32-row blocks straddle shapes: a one-hot
         sid = torch.arange(S, device=dev)[:, None, None]   # product sums each shape's rows
-        owner_pad = torch.full((Np,), S, device=dev, dtype=torch.long)
-        owner_pad[:N] = torch.arange(S, device=dev).repeat_interleave(P)
+        owner_pad = _owner_index(S, lay.P, Np, dev)
         onehot = (owner_pad.view(1, nblk, KT) == sid).to(torch.bfloat16).permute(1, 0, 2)
         onehot = onehot.contiguous()               # blocked [nblk][S][KT]
     for l in range(7, -1, -1):
-        # g_cur = dL/d pre_l (bf16, both layouts); its column sums are colsums[l]
-        gcs[l] = colsums[l]
-        wout = hsp if l == skip - 1 else H
+        # g = dL/d pre_l (bf16, both layouts); its column sums are gcs[l]
+        xT = ZxT if l == 0 else hT[l - 1]
         if l == skip:
-            gw["W4h"] = torch.empty(H, hsp, **f32)
-            gw["W4z"] = torch.empty(H, zw, **f32)
-            probs = [wgrad(gT_cur, hT[l - 1], H, hsp, gw["W4h"], 0),
-                     wgrad(gT_cur, ZxT, H, zw, gw["W4z"], 1)]
-        elif l == 0:
-            gw["W0"] = torch.empty(H, zw, **f32)
-            probs = [wgrad(gT_cur, ZxT, H, zw, gw["W0"], 0)]
+            gw["W4h"] = torch.empty(H, lay.hsp, **f32)
+            gw["W4z"] = torch.empty(H, lay.zw, **f32)
+            probs = [wg(gT, xT, H, lay.hsp, gw["W4h"], 0),
+                     wg(gT, ZxT, H, lay.zw, gw["W4z"], 1)]
         else:
-            win = h[l - 1].shape[1]
+            wout, win = gT.shape[1], xT.shape[1]
             gw[f"W{l}"] = torch.empty(wout, win, **f32)
-            probs = [wgrad(gT_cur, hT[l - 1], wout, win, gw[f"W{l}"], 0)]
+            probs = [wg(gT, xT, wout, win, gw[f"W{l}"], 0)]
         if onehot is not None and l in (skip, 0):
             Gs[l] = torch.empty(S, H, **f32)
-            probs.append(wgrad(onehot, gT_cur, S, H, Gs[l], len(probs)))
+            probs.append(wg(onehot, gT, S, H, Gs[l], len(probs)))
         # weight gradients (long K per slice): larger tiles than the 1M-row G W product, so
         # their own launch
         ops.gemm(probs, tile=wgrad_tile)
         if l > 0:
-            win = h[l - 1].shape[1]
-            WdT = WT["W4h"] if l == skip else WT[f"W{l}"]          # [win, wout]
-            g_nxt = torch.empty(Np, win, **bf)
-            gT_nxt = torch.empty(nblk, win, KT, **bf)
-            cs = torch.empty(nrow32, win, **f32)
-            ops.gemm([ops.gemm_problem([(g_cur, WdT)], Np, win, mode="relu_bwd", M_valid=N,
-                                       Rb=h[l - 1], Cb=g_nxt, CbT=gT_nxt, colsum=cs,
-                                       ct_blk=KT)])
-            colsums[l - 1] = cs
-        if l > 0:
-            g_prev_keep = (g_cur, gT_cur)            # noqa: F841 (alive until the launch is queued)
-            g_cur, gT_cur = g_nxt, gT_nxt
+            g, gT, gcs[l - 1] = _gw_relu_bwd(g, WT["W4h" if l == skip else f"W{l}"], h[l - 1],
+                                             lay)
+    return gw, gcs, Gs
+
+
+def _bias_sums_bf16(gcs, gw) -> None:
+    """``gw["b{l}"]``, l = 0..7: the column sums of the 32-row partials ``gcs[l]``."""
     for l in range(8):
-        width = gcs[l].shape[1]
-        gb[f"b{l}"] = torch.empty(width, **f32)
-        ops.colsum(gcs[l], gb[f"b{l}"])
+        gw[f"b{l}"] = torch.empty(gcs[l].shape[1], device=gcs[l].device, dtype=torch.float32)
+        ops.colsum(gcs[l], gw[f"b{l}"])
 
-    # ---- latent gradient: per shape sum_p (g4 W4z + g0 W0)[:, :L]
-    if onehot is None:                             # shape s = 32-row blocks [s P/32, (s+1) P/32)
+
+def _latent_grad_bf16(masters, gcs, Gs, lay: _Layout):
+    """gz [S, L] without an [N, L] product: per shape, sum_p (g4 W4z + g0 W0)[:, :L] = (the
+    per-shape column sums of g4 and g0) x the masters' latent columns, [S, H] x [H, L] in fp32."""
+    L, skip, S, hs = lay.L, lay.skip, lay.S, lay.hs
+    f32 = dict(device=gcs[0].device, dtype=torch.float32)
+    if not lay.P % 32:                             # shape s = 32-row blocks [s P/32, (s+1) P/32)
+        Gs = {}
         for l in (skip, 0):
-            Gs[l] = torch.empty(S, H, **f32)
-            ops.colsum_segments(gcs[l][:N // 32].contiguous(), S, Gs[l])
-    G4, G0 = Gs[skip], Gs[0]
+            Gs[l] = torch.empty(S, lay.H, **f32)
+            ops.colsum_segments(gcs[l][:lay.N // 32].contiguous(), S, Gs[l])
     gz = torch.empty(S, L, **f32)
-    Wm = masters[f"W{skip}"]
-    ops.linear(G4, Wm[:, hs:hs + L].t(), gz, compute=capi.COMPUTE_FP32)
-    ops.linear(G0, masters["W0"][:, :L].t(), gz, epi=capi.EPI_ACCUM, compute=capi.COMPUTE_FP32)
-    coef = reg_lambda * min(1.0, epoch / 100.0) / S
-    if coef != 0.0:
-        ops.latent_l2_reg(z, coef, loss, gz)
-
-    if grads is None:
-        grads = {k: torch.empty_like(v) for k, v in masters.items()}
-    grads["W0"].copy_(gw["W0"][:, :L + 3])
-    for l in range(1, 9):
-        if l == skip - 1:
-            grads[f"W{l}"].copy_(gw[f"W{l}"][:hs])
-            grads[f"b{l}"].copy_(gb[f"b{l}"][:hs])
-            continue
-        if l == skip:
-            grads[f"W{l}"][:, :hs].copy_(gw["W4h"][:, :hs])
-            grads[f"W{l}"][:, hs:].copy_(gw["W4z"][:, :L + 3])
-        else:
-            grads[f"W{l}"].copy_(gw[f"W{l}"].reshape(grads[f"W{l}"].shape))
-        grads[f"b{l}"].copy_(gb[f"b{l}"].reshape(grads[f"b{l}"].shape))
-    grads["b0"].copy_(gb["b0"])
-    return loss, grads, gz
+    ops.linear(Gs[skip], masters[f"W{skip}"][:, hs:hs + L].t(), gz, compute=capi.COMPUTE_FP32)
+    ops.linear(Gs[0], masters["W0"][:, :L].t(), gz, epi=capi.EPI_ACCUM,
+               compute=capi.COMPUTE_FP32)
+    return gz
 
 
 @dataclass
@@ -526,11 +528,7 @@ def train_autodecoder(decoder: SDFDecoder, xyz: torch.Tensor, sdf: torch.Tensor,
         state.lat_optimizer.step()
         state.step += 1
         state.losses.append(loss)
-    pend = [i for i, l in enumerate(state.losses) if isinstance(l, torch.Tensor)]
-    if pend:                     # one device->host transfer for the whole run
-        vals = torch.cat([state.losses[i].reshape(1).float() for i in pend]).tolist()
-        for i, v in zip(pend, vals):
-            state.losses[i] = v
+    ops.read_back_losses(state.losses)
     for l in range(9):
         decoder.weights[l] = state.masters[f"W{l}"].detach().to("cpu").contiguous()
         decoder.biases[l] = state.masters[f"b{l}"].detach().to("cpu").contiguous()

@@ -119,6 +119,5 @@ def fit_latents(decoder: SDFDecoder, xyz: torch.Tensor, sdf: torch.Tensor, *, st
             losses.append(out["loss"])
     lat.grad = None
     if return_losses:
-        vals = torch.cat(losses).tolist() if losses else []     # one device->host transfer
-        return lat, vals
+        return lat, ops.read_back_losses(losses)
     return lat

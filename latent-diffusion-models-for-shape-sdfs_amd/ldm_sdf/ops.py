@@ -25,6 +25,17 @@ def _f32(*ts: torch.Tensor) -> None:
             raise capi.LdmError(f"expected float32, got {t.dtype}")
 
 
+def read_back_losses(losses: list) -> list:
+    """Replace, in place, the entries of ``losses`` that are still device tensors (one value
+    each) by floats: one device->host transfer for a whole run, not one per step."""
+    pend = [i for i, l in enumerate(losses) if isinstance(l, torch.Tensor)]
+    if pend:
+        vals = torch.cat([losses[i].reshape(1).float() for i in pend]).tolist()
+        for i, v in zip(pend, vals):
+            losses[i] = v
+    return losses
+
+
 # ---------------------------------------------------------------------------------------- A1
 def grid_coords(N: int, k0: int = 0, k1: Optional[int] = None, bbox=(-1.0, 1.0),
                 device=None) -> torch.Tensor:

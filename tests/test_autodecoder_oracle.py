@@ -72,27 +72,68 @@ def test_oracle_gradients_match_finite_differences():
     assert loss > 0
 
 
-def test_work_layout_round_trip():
-    """work_weights pads, master_grads cuts back: with the padded weights fed back in as
-    'gradients' the masters come out unchanged, and every pad is zero."""
-    from ldm_sdf.autodecoder import master_grads, work_weights
-    L, H, skip = 256, 512, 4
-    dims = R.decoder_layer_dims(L, H)
+def _random_masters(L=256, H=512):
     g = torch.Generator().manual_seed(5)
     m = {}
-    for l, (i, o) in enumerate(dims):
+    for l, (i, o) in enumerate(R.decoder_layer_dims(L, H)):
         m[f"W{l}"] = torch.randn(o, i, generator=g)
         m[f"b{l}"] = torch.randn(o, generator=g)
-    w = work_weights(m, L, H, skip, torch.float32)
-    assert tuple(w["W0"].shape) == (H, 264) and float(w["W0"][:, 259:].abs().sum()) == 0
-    assert tuple(w["W3"].shape) == (256, H) and float(w["W3"][253:].abs().sum()) == 0
+    return m
+
+
+# (working dtype, (row_pad, col_pad) or None for work_weights' defaults, zw): the fp32 path's
+# pads, the bf16 path's pads on exact fp32 values, and the bf16 path as it runs
+@pytest.mark.parametrize("dtype,pads,zw", [(torch.float32, None, 264),
+                                           (torch.float32, (64, 64), 320),
+                                           (torch.bfloat16, (64, 64), 320)],
+                         ids=["fp32-4-8", "fp32-64-64", "bf16-64-64"])
+def test_work_layout_round_trip(dtype, pads, zw):
+    """work_weights pads, master_grads cuts back: every shape is the padded one, every pad is
+    zero, every other element is the master's in the working dtype, and with the padded weights
+    fed back in as 'gradients' the masters (rounded to the working dtype) come out unchanged."""
+    from ldm_sdf.autodecoder import master_grads, work_weights
+    L, H, skip, hs = 256, 512, 4, 253
+    m = _random_masters(L, H)
+    w = work_weights(m, L, H, skip, dtype, *(pads or ()))
+    assert {k: tuple(w[k].shape) for k in ("W0", "W3", "W4h", "W4z", "b3p")} == {
+        "W0": (H, zw), "W3": (256, H), "W4h": (H, 256), "W4z": (H, zw), "b3p": (256,)}
+    assert float(w["W0"][:, 259:].abs().sum()) == 0
+    assert float(w["W3"][253:].abs().sum()) == 0
     assert float(w["b3p"][253:].abs().sum()) == 0
     assert float(w["W4h"][:, 253:].abs().sum()) == 0 and float(w["W4z"][:, 259:].abs().sum()) == 0
+    assert all(w[k].dtype == dtype for k in w if k != "b3p") and w["b3p"].dtype == torch.float32
+    assert torch.equal(w["W4h"][:, :hs], m["W4"][:, :hs].to(dtype))
+    assert torch.equal(w["W4z"][:, :L + 3], m["W4"][:, hs:].to(dtype))
     gw = dict(w)
     for l in range(9):
         gw[f"b{l}"] = m[f"b{l}"]
     gw["b3"] = w["b3p"]
     out = {k: torch.empty_like(v) for k, v in m.items()}
-    master_grads(gw, L, skip, 253, out)
+    master_grads(gw, L, skip, hs, out)
     for k in m:
-        assert torch.equal(out[k], m[k]), k
+        want = m[k] if k.startswith("b") else m[k].to(dtype).float()
+        assert torch.equal(out[k], want), k
+
+
+def test_layout_matches_the_emulations():
+    """The product's one layout record: the fp32 pads give hsp 256 / zw 264 with no row padding
+    or blocking; the bf16 blocking of the sample axis is the emulation's independent
+    restatement (E.layout) and the expected (N, Np, KT, nblk) on every GPU-test case and on the
+    benchmark's 64 x 16384."""
+    from ldm_sdf import autodecoder as AD
+    from tests import autodecoder_emulation as E
+    assert (AD._KQ, AD._KSEG) == (E._KQ, 64)
+    f = AD._layout(256, 512, 4, 253, 3, 129, torch.float32)
+    assert (f.row_pad, f.col_pad, f.hs, f.hsp, f.zw) == (4, 8, 253, 256, 264)
+    assert (f.N, f.Np, f.KT, f.nblk) == (387, 387, 387, 1)
+    want = {E.CASE_1x64[:2]: (64, 128, 128, 1), E.CASE_5x96[:2]: (480, 512, 512, 1),
+            E.CASE_3x256[:2]: (768, 768, 256, 3), E.CASE_3x200[:2]: (600, 640, 128, 5),
+            E.CASE_2x129[:2]: (258, 384, 128, 3), E.CASE_320xP[:2]: (23040, 23040, 512, 45),
+            (64, 16384): (1048576, 1048576, 8192, 128)}
+    assert set(c[:2] for c in E.CASES) < set(want)
+    for (S, P), nums in want.items():
+        b = AD._layout(E.L, E.H, E.SKIP, 253, S, P, torch.bfloat16)
+        assert (b.row_pad, b.col_pad, b.hs, b.hsp, b.zw) == (64, 64, 253, 256, 320)
+        assert (b.N, b.Np, b.KT, b.nblk) == nums, (S, P)
+        e = E.layout(S, P)
+        assert (e["N"], e["Np"], e["KT"], e["nblk"]) == nums, (S, P)

@@ -206,8 +206,8 @@ def test_train_step_bf16_split_k_workspaces_distinct(dev):
     case = E.CASE_320xP
     S, P = case[0], case[1]
     lay = _layout(case)
-    zw = -(-(E.L + 3) // AD._KSEG) * AD._KSEG
-    assert S == zw and P % 32 != 0 and lay["nblk"] > 1
+    zw = AD._layout(E.L, E.H, E.SKIP, E.H - E.L - 3, S, P, torch.bfloat16).zw
+    assert S == zw == 320 and P % 32 != 0 and lay["nblk"] > 1
     p, z, xyz, sdf, _ = E.inputs(case)
     want_loss, want = E.reference(case)
     loss, got = _step(dev, case, "bf16")
