@@ -602,6 +602,47 @@ typedef struct ldm_conv1d_args {
 } ldm_conv1d_args_t;
 int ldm_conv1d(const ldm_conv1d_args_t* a, ldm_stream_t s);
 
+/* ---- C17 training: the backward of the fused conv (csrc/unet_bwd.hip) ----- */
+/* Data gradient of ONE forward segment (the ldm_conv1d_seg_t of the forward call: X is read for
+ * SiLU' only when silu_in; W is the forward's packed weight at the segment's channel offset,
+ * fp32 or bf16 storage):
+ *   dX[b][ci][p] (=|+=) act'(X[b][ci][p]) * sum_co sum_k sum_{l : src(l,k) = p}
+ *                                                       W(co,ci,k) * dY[b][co][l]
+ * act' = SiLU' if silu_in else 1; accumulate != 0 adds to dX (an activation with several
+ * consumers takes its gradients through successive calls, in the caller's order: no atomics).
+ * Geometries: those of ldm_conv1d (ksize 1 / 3 stride 1, ksize 3 / 4 stride 2, LDM_CONV_UP2);
+ * any other ksize / stride: LDM_ENOSYS.  W must sit at a multiple of 16 channels (LDM_EALIGN),
+ * ldw and kstride must be multiples of 16. */
+typedef struct ldm_conv1d_bwd_data_args {
+    int32_t B, Cout, L_out, w_dtype, accumulate, reserved;
+    ldm_conv1d_seg_t seg;
+    const float* dY;                  /* [B][Cout][L_out] */
+    float* dX;                        /* [B][seg.C][seg.L_in] */
+} ldm_conv1d_bwd_data_args_t;
+int ldm_conv1d_bwd_data(const ldm_conv1d_bwd_data_args_t* a, ldm_stream_t s);
+
+/* Weight gradient of ONE forward conv, all its segments sharing dY (seg[i].W is not read):
+ *   dW_s(co,ci,k) = sum_b sum_l dY[b][co][l] * act_s(Xsrc_s(b,ci,l,k))
+ * written fp32 in the forward's packed layout: dW[i] points into a [Cout16][ksize][Cw16] buffer at
+ * the segment's channel offset (pitches seg[i].ldw / kstride), and the call writes the segment's
+ * round16(C) columns of all Cout16 rows and taps, zeros in the padding.  dbias[co] = sum_{b,l} dY
+ * and dcbias[b][co] = sum_l dY[b][co][l] when not NULL.  The contraction over B * L_out is split
+ * over workgroups into fp32 partials in ws and reduced in fixed order: the result is a pure
+ * function of the inputs.  ws needs ldm_conv1d_bwd_weight_ws_floats(a) floats (LDM_ENOSPC). */
+typedef struct ldm_conv1d_bwd_weight_args {
+    int32_t B, Cout, L_out, n_seg;
+    ldm_conv1d_seg_t seg[LDM_CONV_MAX_SEGS];
+    float* dW[LDM_CONV_MAX_SEGS];
+    const float* dY;                  /* [B][Cout][L_out] */
+    float* dbias;                     /* [Cout] or NULL */
+    float* dcbias;                    /* [B][Cout] or NULL */
+    float* ws; int64_t ws_floats;
+} ldm_conv1d_bwd_weight_args_t;
+/* 0 for invalid args.  S * sum_s Cout16 * ksize_s * round16(C_s), S = min(64, B * ceil(L_out / 64))
+ * slices, + B * Cout when dbias is asked for without dcbias. */
+int64_t ldm_conv1d_bwd_weight_ws_floats(const ldm_conv1d_bwd_weight_args_t* a);
+int ldm_conv1d_bwd_weight(const ldm_conv1d_bwd_weight_args_t* a, ldm_stream_t s);
+
 /* (ABI 6: the round-3 one-launch UNet sampling loop, ldm_unet_loop*, was retired -- at 0.53x the
  * hipGraph of ldm_conv1d launches after the round-4 conv staging) */
 

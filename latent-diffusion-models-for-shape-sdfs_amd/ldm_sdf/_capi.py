@@ -139,6 +139,19 @@ class ConvArgs(C.Structure):
                 ("c1", _vp), ("c2", _vp), ("sigma", _vp), ("t", C.c_int32)]
 
 
+class ConvBwdDataArgs(C.Structure):
+    _fields_ = [("B", C.c_int32), ("Cout", C.c_int32), ("L_out", C.c_int32),
+                ("w_dtype", C.c_int32), ("accumulate", C.c_int32), ("reserved", C.c_int32),
+                ("seg", ConvSeg), ("dY", _vp), ("dX", _vp)]
+
+
+class ConvBwdWeightArgs(C.Structure):
+    _fields_ = [("B", C.c_int32), ("Cout", C.c_int32), ("L_out", C.c_int32),
+                ("n_seg", C.c_int32), ("seg", ConvSeg * CONV_MAX_SEGS),
+                ("dW", _vp * CONV_MAX_SEGS), ("dY", _vp), ("dbias", _vp), ("dcbias", _vp),
+                ("ws", _vp), ("ws_floats", C.c_int64)]
+
+
 # (name, restype, argtypes) -- every symbol include/ldm_sdf.h declares.
 _i, _sz, _f = C.c_int, C.c_size_t, C.c_float
 SIGNATURES = [
@@ -187,6 +200,9 @@ SIGNATURES = [
     ("ldm_colsum_segments", _i, [_fp, _i, _i, _i, _fp, _i, _vp]),
     ("ldm_latent_l2_reg", _i, [_fp, _i, _i, _f, _fp, _fp, _vp]),
     ("ldm_conv1d", _i, [C.POINTER(ConvArgs), _vp]),
+    ("ldm_conv1d_bwd_data", _i, [C.POINTER(ConvBwdDataArgs), _vp]),
+    ("ldm_conv1d_bwd_weight_ws_floats", C.c_int64, [C.POINTER(ConvBwdWeightArgs)]),
+    ("ldm_conv1d_bwd_weight", _i, [C.POINTER(ConvBwdWeightArgs), _vp]),
     ("ldm_gemm_bf16", _i, [C.POINTER(GemmArgs), _vp]),
     ("ldm_denoiser_train_ws_bytes", _sz, [C.POINTER(Denoiser), _i]),
     ("ldm_denoiser_fwd", _i, [C.POINTER(Denoiser), _fp, _vp, _i, _fp, _vp, _vp]),

@@ -24,6 +24,7 @@ from . import _capi as capi
 from . import dist as ldist
 from . import ops
 from .models import DDPMSchedule, MLPDenoiser, SDFDecoder
+from .unet import UNet1DDenoiser, UNetTrainer, make_work
 
 
 # ---------------------------------------------------------------------------------- decode
@@ -302,6 +303,9 @@ class TrainState:
     adam_grads: Optional[Dict[str, torch.Tensor]] = None
     adam_pack: Optional[Dict[str, object]] = None    # the device pack the table points into
     graphs: Optional[Dict[str, object]] = None       # captured steps (train(graph=True))
+    # a UNet1DDenoiser's state keeps masters and moments in its training layout (convs packed,
+    # DESIGN.md §15); the denoiser converts them to and from torch layout for save / load
+    codec: Optional[object] = None
 
     # ---- checkpoint / resume ({denoiser, optimizer, step, rng}) --------------
     FORMAT = "ldm_sdf.TrainState/1"
@@ -315,12 +319,12 @@ class TrainState:
         AdamW descriptor tables, graphs) is rebuilt after a load, never saved."""
         if self.masters is None:
             raise ValueError("TrainState.save: nothing trained yet")
+        exp = (lambda n, v: v.detach().cpu()) if self.codec is None else self.codec.export_tensor
         ck = {"format": self.FORMAT, "step": int(self.step),
               "losses": [float(l) for l in self.losses], "hparams": dict(self.hparams),
-              "masters": {n: v.detach().cpu() for n, v in self.masters.items()}}
+              "masters": {n: exp(n, v) for n, v in self.masters.items()}}
         if self.adam is not None:
-            ck["adam"] = {n: (m.detach().cpu(), v.detach().cpu())
-                          for n, (m, v) in self.adam.items()}
+            ck["adam"] = {n: (exp(n, m), exp(n, v)) for n, (m, v) in self.adam.items()}
         if self.optimizer is not None:
             ck["optimizer"] = self.optimizer.state_dict()
             # the state dict is positional: record which parameter each position is, so a load
@@ -335,7 +339,7 @@ class TrainState:
         torch.save(ck, path)
 
     @classmethod
-    def load(cls, path: str, denoiser: MLPDenoiser, device=None,
+    def load(cls, path: str, denoiser, device=None,
              generator: Optional[torch.Generator] = None,
              optimizer: Optional[torch.optim.Optimizer] = None) -> "TrainState":
         """Restore a state written by ``save`` into ``denoiser`` (its parameters become the
@@ -356,6 +360,23 @@ class TrainState:
         # which parameter each tensor of a caller's optimizer is (by identity, before the
         # denoiser's tensors are replaced): its param_groups are re-pointed at the loaded
         # masters below, so optimizer.step() updates what train() trains
+        if isinstance(denoiser, UNet1DDenoiser):
+            if optimizer is not None or "optimizer" in ck:
+                raise ValueError("TrainState.load: UNet training uses the built-in AdamW only")
+            denoiser.params = {n: ck["masters"][n].to(torch.float32).contiguous() for n in names}
+            denoiser.invalidate()
+            st = cls()
+            st.step, st.losses, st.hparams = int(ck["step"]), list(ck["losses"]), dict(ck["hparams"])
+            st.codec = denoiser
+            st.masters = denoiser.train_masters(device)
+            st.adam = {n: (denoiser.import_tensor(n, m, device),
+                           denoiser.import_tensor(n, v, device))
+                       for n, (m, v) in ck["adam"].items()}
+            if generator is not None:
+                if "rng" not in ck:
+                    raise ValueError(f"{path}: no generator state saved")
+                generator.set_state(ck["rng"])
+            return st
         opt_names = None
         if optimizer is not None:
             ident = {id(t): n for n, t in denoiser.params.items()}
@@ -429,7 +450,7 @@ def _reduce_grads(denoiser, grads, loss, B_local: int, global_batch: Optional[in
     return lslot.clone()
 
 
-def train_step(denoiser: MLPDenoiser, schedule: DDPMSchedule, x0: torch.Tensor,
+def train_step(denoiser, schedule: DDPMSchedule, x0: torch.Tensor,
                t: torch.Tensor, eps: torch.Tensor, *, dtype: str = "bf16",
                grads: Optional[Dict[str, torch.Tensor]] = None,
                group=None, global_batch: Optional[int] = None
@@ -441,7 +462,20 @@ def train_step(denoiser: MLPDenoiser, schedule: DDPMSchedule, x0: torch.Tensor,
     (each rank weighted by its share; None: the plain mean over ranks).  bf16 runs the fused
     forward + backward C call, ``ldm_denoiser_train_step``, in the form
     ``ops.train_step_config`` selects -- the one-launch job DAG (without its AdamW nodes: the
-    update waits for the all-reduce) or the launch path."""
+    update waits for the all-reduce) or the launch path.
+
+    A ``UNet1DDenoiser`` takes the conv path (``UNetTrainer``): fp32 arithmetic with
+    fp32 or bf16-stored weights, gradients keyed by its parameter names in torch layout, one
+    rank only (a group with more ranks raises)."""
+    if isinstance(denoiser, UNet1DDenoiser):
+        if ldist.world_and_rank(group)[0] > 1:
+            raise ValueError("train_step: data-parallel UNet training is not supported")
+        if grads is not None:
+            raise ValueError("train_step: the UNet returns its own gradient buffers")
+        capi.require_device(x0, t, eps)
+        tr = denoiser.trainer(dtype, x0.device, x0.shape[0])
+        loss = tr.step(schedule.device(x0.device)["desc"], x0, t, eps)
+        return loss, tr.export_grads()
     device = x0.device
     dev = denoiser.device_pack(dtype, device, with_tables=False)
     sd = schedule.device(device)
@@ -477,7 +511,7 @@ def _adam_table(denoiser: MLPDenoiser, state: TrainState, grads, dtype: str, dev
           work.get(n + "_T")) for n, p in state.masters.items()])
 
 
-def train(denoiser: MLPDenoiser, schedule: DDPMSchedule, latents: torch.Tensor, *, steps: int,
+def train(denoiser, schedule: DDPMSchedule, latents: torch.Tensor, *, steps: int,
           batch: Optional[int] = None, lr: float = 1e-4, weight_decay: float = 0.0,
           dtype: str = "bf16", generator: Optional[torch.Generator] = None,
           state: Optional[TrainState] = None, group=None, fused_step: bool = True,
@@ -494,7 +528,20 @@ def train(denoiser: MLPDenoiser, schedule: DDPMSchedule, latents: torch.Tensor, 
     chunk), captured once per state; measured 3% slower than the eager calls at config 2
     (3030 vs 3115 steps/s, scripts/train_ab.py), so off by default.  No switch changes the
     results.
+
+    A ``UNet1DDenoiser`` trains through ``_train_unet`` (single rank, built-in AdamW on masters
+    kept in the conv kernels' packed layout); a group with more than one rank, ``graph`` and
+    ``overlap`` raise for it.  Afterwards ``denoiser.params`` hold the trained weights and
+    ``sample()`` uses them.
     """
+    if isinstance(denoiser, UNet1DDenoiser):
+        if ldist.world_and_rank(group)[0] > 1:
+            raise ValueError("train: data-parallel UNet training is not supported")
+        if graph or overlap:
+            raise ValueError("train: graph / overlap are not available for the UNet")
+        capi.require_device(latents)
+        return _train_unet(denoiser, schedule, latents, steps, batch, lr, weight_decay, dtype,
+                           generator, state)
     capi.require_device(latents)
     device = latents.device
     world, rank = ldist.world_and_rank(group)
@@ -612,6 +659,64 @@ def train(denoiser: MLPDenoiser, schedule: DDPMSchedule, latents: torch.Tensor, 
         denoiser.invalidate_tables()
     elif state.optimizer is None:
         denoiser.invalidate()    # fp32 training updated the masters only: bf16 packs are stale
+    ops.read_back_losses(state.losses)
+    return state
+
+
+def _train_unet(denoiser: UNet1DDenoiser, schedule: DDPMSchedule, latents: torch.Tensor,
+                steps: int, batch: Optional[int], lr: float, weight_decay: float, dtype: str,
+                generator: Optional[torch.Generator], state: Optional[TrainState]) -> TrainState:
+    """``train`` for the 1D-UNet (single rank, built-in AdamW).  Masters, gradients
+    and Adam moments of the conv weights live in the forward's packed layout, so
+    ``ldm_adamw_multi`` (elementwise) updates them in place and its bf16 output IS the pack the
+    next step reads; the padding stays zero (g = m = v = 0 there).  The draws of a step are
+    (batch indices,) t, eps in the MLP path's order, one step at a time, so a run continued
+    from a saved state draws what the uninterrupted run draws; a CPU generator draws on the host."""
+    device = latents.device
+    M, D = latents.shape
+    if D != denoiser.D:
+        raise ValueError(f"latents must be [M, {denoiser.D}]")
+    batch = M if batch is None else batch
+    if state is None:
+        state = TrainState()
+        state.codec = denoiser
+        state.masters = denoiser.train_masters(device)
+        state.adam = {n: (torch.zeros_like(v), torch.zeros_like(v))
+                      for n, v in state.masters.items()}
+        state.hparams = dict(lr=lr, weight_decay=weight_decay)
+    if state.codec is not denoiser or state.optimizer is not None:
+        raise ValueError("train: this state does not belong to this UNet1DDenoiser")
+    key = (dtype, batch, device)
+    if state.adam_pack is None or state.adam_pack["key"] != key:
+        work = make_work(state.masters, dtype)
+        tr = UNetTrainer(denoiser, state.masters, work, batch, device)
+        ents = [(p, tr.grads[n], *state.adam[n],
+                 work[n] if work[n].dtype == torch.bfloat16 else None, None)
+                for n, p in state.masters.items()]
+        cap = capi.ADAMW_MAX_TENSORS          # ~50 tensors: two launches
+        state.adam_pack = {"key": key, "trainer": tr, "work": work}
+        state.adam_table = [ops.adamw_table(ents[i:i + cap]) for i in range(0, len(ents), cap)]
+        state.adam_grads = tr.grads
+    tr = state.adam_pack["trainer"]
+    sdesc = schedule.device(device)["desc"]
+    gdev = generator.device if generator is not None else device
+    T = schedule.T
+    for _ in range(steps):
+        idx = torch.randint(0, M, (1, batch), device=gdev, generator=generator) \
+            if batch != M else None
+        t = torch.randint(0, T, (1, batch), device=gdev, generator=generator, dtype=torch.int32)
+        eps = torch.randn(1, batch, D, device=gdev, generator=generator)
+        x0 = latents[idx[0].to(device)] if idx is not None else latents
+        loss = tr.step(sdesc, x0, t[0].to(device), eps[0].to(device))
+        for tab in state.adam_table:
+            ops.adamw_multi(tab, lr=state.hparams["lr"],
+                            weight_decay=state.hparams["weight_decay"], step=state.step + 1,
+                            device=device)
+        state.step += 1
+        state.losses.append(loss)
+    # the trained weights in torch layout; the sampling packs and E tables are rebuilt from them
+    denoiser.params = {n: denoiser.export_tensor(n, v) for n, v in state.masters.items()}
+    denoiser.invalidate()
     ops.read_back_losses(state.losses)
     return state
 

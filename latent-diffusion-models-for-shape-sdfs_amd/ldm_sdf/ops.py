@@ -743,6 +743,120 @@ def conv1d(segs, Y: torch.Tensor, **kw) -> torch.Tensor:
     return Y
 
 
+# ------------------------------------------------------------------- C17 training
+def unpack_conv_weight(Wp: torch.Tensor, Cout: int, Cw: int) -> torch.Tensor:
+    """The inverse of ``pack_conv_weight`` on the unpadded part: packed ``[Cout16, K, Cw16]`` ->
+    torch layout ``[Cout, Cw, K]`` (contiguous)."""
+    if Wp.dim() != 3 or Wp.shape[0] != _r16(Cout) or Wp.shape[2] != _r16(Cw):
+        raise capi.LdmError(f"unpack_conv_weight: {tuple(Wp.shape)} is not the packing of "
+                            f"[{Cout}, {Cw}, K]")
+    idx = perm16_index(_r16(Cw))[:Cw].to(Wp.device)
+    return Wp[:Cout][:, :, idx].permute(0, 2, 1).contiguous()
+
+
+def _bwd_seg(g: capi.ConvSeg, s: "ConvSegment", i: int, B: int, Cout: int, L_out: int,
+             what: str) -> None:
+    """Fill the C segment of a backward call from the forward's ``ConvSegment`` (its ``W`` is
+    the forward's packed weight, or any tensor of that shape)."""
+    X, W = s.X, s.W
+    _f32(X)
+    _contig(X, W)
+    if X.dim() != 3 or X.shape[0] != B or W.dim() != 3 or W.shape[0] != _r16(Cout) \
+            or W.shape[2] % 16:
+        raise capi.LdmError(f"{what} seg {i}: X [B, C, L_in] / packed weight "
+                            f"[{_r16(Cout)}, K, Cw16] expected (got {tuple(X.shape)}, "
+                            f"{tuple(W.shape)})")
+    Cs = X.shape[1]
+    if s.c_off % 16 or s.c_off + Cs > W.shape[2]:
+        raise capi.LdmError(f"{what} seg {i}: channels {s.c_off}+{Cs} vs {W.shape[2]}")
+    Lsrc = 2 * X.shape[2] if s.mode == capi.CONV_UP2 else X.shape[2]
+    if (Lsrc + 2 * s.pad - s.ksize) // s.stride + 1 != L_out:
+        raise capi.LdmError(f"{what} seg {i}: L_in {X.shape[2]} does not give L_out {L_out}")
+    g.X = X.data_ptr()
+    g.W = W.data_ptr() + s.c_off * W.element_size()
+    g.C, g.L_in, g.ksize, g.stride, g.pad = Cs, X.shape[2], s.ksize, s.stride, s.pad
+    g.mode, g.silu_in = s.mode, int(bool(s.silu))
+    g.ldw, g.kstride = s.ksize * W.shape[2], W.shape[2]
+
+
+def conv1d_bwd_data_args(seg: "ConvSegment", dY: torch.Tensor, dX: torch.Tensor,
+                         accumulate: bool = False) -> capi.ConvBwdDataArgs:
+    capi.require_device(dY, dX, seg.X, seg.W)
+    _f32(dY, dX)
+    _contig(dY, dX)
+    if dY.dim() != 3 or dX.shape != seg.X.shape:
+        raise capi.LdmError("conv1d_bwd_data: dY must be [B, Cout, L_out] and dX shaped as X")
+    B, Cout, L_out = dY.shape
+    a = capi.ConvBwdDataArgs()
+    a.B, a.Cout, a.L_out, a.accumulate = B, Cout, L_out, int(bool(accumulate))
+    a.w_dtype = {torch.float32: capi.LDM_F32, torch.bfloat16: capi.LDM_BF16}.get(seg.W.dtype, -1)
+    if a.w_dtype < 0:
+        raise capi.LdmError(f"conv1d_bwd_data: weight dtype {seg.W.dtype}")
+    _bwd_seg(a.seg, seg, 0, B, Cout, L_out, "conv1d_bwd_data")
+    a.dY, a.dX = dY.data_ptr(), dX.data_ptr()
+    return a
+
+
+def conv1d_bwd_data(seg: "ConvSegment", dY: torch.Tensor, dX: torch.Tensor,
+                    accumulate: bool = False) -> torch.Tensor:
+    """``dX (=|+=) act'(X) * conv^T(dY; W)`` for one forward segment (``ldm_conv1d_bwd_data``):
+    ``seg`` is the forward's ``ConvSegment`` (input, packed weight, geometry, SiLU flag)."""
+    a = conv1d_bwd_data_args(seg, dY, dX, accumulate)
+    capi.check(capi.load().ldm_conv1d_bwd_data(C.byref(a), capi.stream_handle(dY.device)),
+               "ldm_conv1d_bwd_data")
+    return dX
+
+
+def conv1d_bwd_weight_args(segs, dY: torch.Tensor, dW_packed, dbias=None, dcbias=None
+                           ) -> capi.ConvBwdWeightArgs:
+    """The call's arguments without a workspace.  ``dW_packed``: one fp32 tensor shaped as the
+    forward's packed weight when every segment reads that one weight, else a list with one such
+    tensor per segment (segments of one weight pass the same tensor)."""
+    if not 1 <= len(segs) <= capi.CONV_MAX_SEGS:
+        raise capi.LdmError("conv1d_bwd_weight: 1..4 segments")
+    dWs = list(dW_packed) if isinstance(dW_packed, (list, tuple)) else [dW_packed] * len(segs)
+    if len(dWs) != len(segs):
+        raise capi.LdmError("conv1d_bwd_weight: one packed gradient per segment")
+    capi.require_device(dY, dbias, dcbias, *dWs, *[s.X for s in segs])
+    _f32(dY, dbias, dcbias, *dWs)
+    _contig(dY, dbias, dcbias, *dWs)
+    if dY.dim() != 3:
+        raise capi.LdmError("conv1d_bwd_weight: dY must be [B, Cout, L_out]")
+    B, Cout, L_out = dY.shape
+    if (dbias is not None and dbias.numel() != Cout) or \
+            (dcbias is not None and tuple(dcbias.shape) != (B, Cout)):
+        raise capi.LdmError("conv1d_bwd_weight: dbias must be [Cout], dcbias [B, Cout]")
+    a = capi.ConvBwdWeightArgs()
+    a.B, a.Cout, a.L_out, a.n_seg = B, Cout, L_out, len(segs)
+    for i, (s, dW) in enumerate(zip(segs, dWs)):
+        if tuple(dW.shape) != tuple(s.W.shape):
+            raise capi.LdmError(f"conv1d_bwd_weight seg {i}: the packed gradient must have the "
+                                f"packed weight's shape {tuple(s.W.shape)}")
+        _bwd_seg(a.seg[i], s, i, B, Cout, L_out, "conv1d_bwd_weight")
+        a.dW[i] = dW.data_ptr() + s.c_off * 4
+    a.dY, a.dbias, a.dcbias = dY.data_ptr(), capi.ptr(dbias), capi.ptr(dcbias)
+    return a
+
+
+def conv1d_bwd_weight_ws_floats(a: capi.ConvBwdWeightArgs) -> int:
+    return int(capi.load().ldm_conv1d_bwd_weight_ws_floats(C.byref(a)))
+
+
+def conv1d_bwd_weight(segs, dY: torch.Tensor, dW_packed, dbias=None, dcbias=None,
+                      ws: Optional[torch.Tensor] = None):
+    """Packed weight gradients of one forward conv (all its segments), and ``dbias [Cout]`` /
+    ``dcbias [B, Cout]`` when given (``ldm_conv1d_bwd_weight``).  Deterministic.  ``ws``: an fp32
+    workspace to reuse (allocated when absent or too small)."""
+    a = conv1d_bwd_weight_args(segs, dY, dW_packed, dbias, dcbias)
+    n = conv1d_bwd_weight_ws_floats(a)
+    if ws is None or ws.numel() < n or ws.dtype != torch.float32 or not ws.is_cuda:
+        ws = torch.empty(max(n, 1), device=dY.device, dtype=torch.float32)
+    a.ws, a.ws_floats = ws.data_ptr(), ws.numel()
+    capi.check(capi.load().ldm_conv1d_bwd_weight(C.byref(a), capi.stream_handle(dY.device)),
+               "ldm_conv1d_bwd_weight")
+    return dW_packed
+
+
 # ---------------------------------------------------------------------------------------- A5
 def temb_forward(dev: Dict[str, object], e: torch.Tensor, H: int,
                  save: Optional[dict] = None, compute: int = capi.COMPUTE_FP32) -> torch.Tensor:
