@@ -25,6 +25,14 @@ def _f32(*ts: torch.Tensor) -> None:
             raise capi.LdmError(f"expected float32, got {t.dtype}")
 
 
+def _w_dtype_code(dt: torch.dtype, what: str) -> int:
+    """The library's code of a weight dtype (fp32 | bf16)."""
+    code = {torch.float32: capi.LDM_F32, torch.bfloat16: capi.LDM_BF16}.get(dt)
+    if code is None:
+        raise capi.LdmError(f"{what}: weight dtype {dt}")
+    return code
+
+
 def read_back_losses(losses: list) -> list:
     """Replace, in place, the entries of ``losses`` that are still device tensors (one value
     each) by floats: one device->host transfer for a whole run, not one per step."""
@@ -424,12 +432,7 @@ def linear(X: torch.Tensor, W: torch.Tensor, Y: torch.Tensor, *, epi: int = capi
     a.Bn, a.M, a.K = Bn, M, K
     a.epi = epi
     a.compute = compute
-    if W.dtype == torch.bfloat16:
-        a.w_dtype = capi.LDM_BF16
-    elif W.dtype == torch.float32:
-        a.w_dtype = capi.LDM_F32
-    else:
-        raise capi.LdmError(f"linear: W dtype {W.dtype}")
+    a.w_dtype = _w_dtype_code(W.dtype, "linear")
     _f32(X, Y, bias, R, A_out, X2)
     a.X, a.sxb, a.sxk = X.data_ptr(), X.stride(0), X.stride(1)
     a.W, a.swm, a.swk = W.data_ptr(), W.stride(0), W.stride(1)
@@ -683,6 +686,30 @@ class ConvSegment:
         self.pad = (self.ksize - 1) // 2 if pad is None else pad
 
 
+def _fill_seg(g: capi.ConvSeg, s: ConvSegment, i: int, B: int, Cout: int, L_out: int,
+              what: str) -> None:
+    """Check one ``ConvSegment`` against the call's ``[B, Cout, L_out]`` and fill its C struct
+    (forward and both backward calls; a backward's ``W`` is the forward's packed weight)."""
+    X, W = s.X, s.W
+    _f32(X)
+    _contig(X, W)
+    xs, ws = tuple(X.shape), tuple(W.shape)
+    if len(xs) != 3 or xs[0] != B or len(ws) != 3 or ws[0] != _r16(Cout) or ws[2] % 16:
+        raise capi.LdmError(f"{what} seg {i}: X [B, C, L_in] / packed weight "
+                            f"[{_r16(Cout)}, K, Cw16] expected (got {xs}, {ws})")
+    (_, Cs, L_in), Cw = xs, ws[2]
+    if s.c_off % 16 or s.c_off + Cs > Cw:
+        raise capi.LdmError(f"{what} seg {i}: channels {s.c_off}+{Cs} vs {Cw}")
+    Lsrc = 2 * L_in if s.mode == capi.CONV_UP2 else L_in
+    if (Lsrc + 2 * s.pad - s.ksize) // s.stride + 1 != L_out:
+        raise capi.LdmError(f"{what} seg {i}: L_in {L_in} does not give L_out {L_out}")
+    g.X = X.data_ptr()
+    g.W = W.data_ptr() + s.c_off * W.element_size()
+    g.C, g.L_in, g.ksize, g.stride, g.pad = Cs, L_in, s.ksize, s.stride, s.pad
+    g.mode, g.silu_in = s.mode, int(bool(s.silu))
+    g.ldw, g.kstride = s.ksize * Cw, Cw
+
+
 def conv1d_args(segs, Y: torch.Tensor, *, bias=None, bias2=None, cbias=None, scb: int = 0,
                 R=None, epi: int = capi.CONV_EPI_STORE, xlat=None, z=None, sched=None,
                 t: int = 0) -> capi.ConvArgs:
@@ -695,29 +722,11 @@ def conv1d_args(segs, Y: torch.Tensor, *, bias=None, bias2=None, cbias=None, scb
     a = capi.ConvArgs()
     a.B, a.Cout, a.L_out, a.n_seg, a.epi = B, Cout, L_out, len(segs), epi
     wdt = segs[0].W.dtype
-    a.w_dtype = {torch.float32: capi.LDM_F32, torch.bfloat16: capi.LDM_BF16}.get(wdt, -1)
-    if a.w_dtype < 0:
-        raise capi.LdmError(f"conv1d: weight dtype {wdt}")
+    a.w_dtype = _w_dtype_code(wdt, "conv1d")
     for i, s in enumerate(segs):
-        X, W = s.X, s.W
-        _f32(X)
-        _contig(X, W)
-        if W.dtype != wdt or W.dim() != 3 or W.shape[0] != _r16(Cout) or X.shape[0] != B \
-                or W.shape[2] % 16:
-            raise capi.LdmError(f"conv1d seg {i}: packed weight [{_r16(Cout)}, K, Cw16] / "
-                                f"batch mismatch (got {tuple(W.shape)})")
-        Cs = X.shape[1]
-        if s.c_off % 16 or s.c_off + Cs > W.shape[2]:
-            raise capi.LdmError(f"conv1d seg {i}: channels {s.c_off}+{Cs} vs {W.shape[2]}")
-        Lsrc = 2 * X.shape[2] if s.mode == capi.CONV_UP2 else X.shape[2]
-        if (Lsrc + 2 * s.pad - s.ksize) // s.stride + 1 != L_out:
-            raise capi.LdmError(f"conv1d seg {i}: L_in {X.shape[2]} does not give L_out {L_out}")
-        g = a.seg[i]
-        g.X = X.data_ptr()
-        g.W = W.data_ptr() + s.c_off * W.element_size()
-        g.C, g.L_in, g.ksize, g.stride, g.pad = Cs, X.shape[2], s.ksize, s.stride, s.pad
-        g.mode, g.silu_in = s.mode, int(bool(s.silu))
-        g.ldw, g.kstride = s.ksize * W.shape[2], W.shape[2]
+        if s.W.dtype != wdt:
+            raise capi.LdmError(f"conv1d seg {i}: weight dtype {s.W.dtype} vs {wdt}")
+        _fill_seg(a.seg[i], s, i, B, Cout, L_out, "conv1d")
     for name, v in (("bias", bias), ("bias2", bias2), ("R", R), ("xlat", xlat), ("z", z)):
         setattr(a, name, capi.ptr(v))
     if R is not None and R.shape != Y.shape:
@@ -754,31 +763,6 @@ def unpack_conv_weight(Wp: torch.Tensor, Cout: int, Cw: int) -> torch.Tensor:
     return Wp[:Cout][:, :, idx].permute(0, 2, 1).contiguous()
 
 
-def _bwd_seg(g: capi.ConvSeg, s: "ConvSegment", i: int, B: int, Cout: int, L_out: int,
-             what: str) -> None:
-    """Fill the C segment of a backward call from the forward's ``ConvSegment`` (its ``W`` is
-    the forward's packed weight, or any tensor of that shape)."""
-    X, W = s.X, s.W
-    _f32(X)
-    _contig(X, W)
-    if X.dim() != 3 or X.shape[0] != B or W.dim() != 3 or W.shape[0] != _r16(Cout) \
-            or W.shape[2] % 16:
-        raise capi.LdmError(f"{what} seg {i}: X [B, C, L_in] / packed weight "
-                            f"[{_r16(Cout)}, K, Cw16] expected (got {tuple(X.shape)}, "
-                            f"{tuple(W.shape)})")
-    Cs = X.shape[1]
-    if s.c_off % 16 or s.c_off + Cs > W.shape[2]:
-        raise capi.LdmError(f"{what} seg {i}: channels {s.c_off}+{Cs} vs {W.shape[2]}")
-    Lsrc = 2 * X.shape[2] if s.mode == capi.CONV_UP2 else X.shape[2]
-    if (Lsrc + 2 * s.pad - s.ksize) // s.stride + 1 != L_out:
-        raise capi.LdmError(f"{what} seg {i}: L_in {X.shape[2]} does not give L_out {L_out}")
-    g.X = X.data_ptr()
-    g.W = W.data_ptr() + s.c_off * W.element_size()
-    g.C, g.L_in, g.ksize, g.stride, g.pad = Cs, X.shape[2], s.ksize, s.stride, s.pad
-    g.mode, g.silu_in = s.mode, int(bool(s.silu))
-    g.ldw, g.kstride = s.ksize * W.shape[2], W.shape[2]
-
-
 def conv1d_bwd_data_args(seg: "ConvSegment", dY: torch.Tensor, dX: torch.Tensor,
                          accumulate: bool = False) -> capi.ConvBwdDataArgs:
     capi.require_device(dY, dX, seg.X, seg.W)
@@ -789,10 +773,8 @@ def conv1d_bwd_data_args(seg: "ConvSegment", dY: torch.Tensor, dX: torch.Tensor,
     B, Cout, L_out = dY.shape
     a = capi.ConvBwdDataArgs()
     a.B, a.Cout, a.L_out, a.accumulate = B, Cout, L_out, int(bool(accumulate))
-    a.w_dtype = {torch.float32: capi.LDM_F32, torch.bfloat16: capi.LDM_BF16}.get(seg.W.dtype, -1)
-    if a.w_dtype < 0:
-        raise capi.LdmError(f"conv1d_bwd_data: weight dtype {seg.W.dtype}")
-    _bwd_seg(a.seg, seg, 0, B, Cout, L_out, "conv1d_bwd_data")
+    a.w_dtype = _w_dtype_code(seg.W.dtype, "conv1d_bwd_data")
+    _fill_seg(a.seg, seg, 0, B, Cout, L_out, "conv1d_bwd_data")
     a.dY, a.dX = dY.data_ptr(), dX.data_ptr()
     return a
 
@@ -832,7 +814,7 @@ def conv1d_bwd_weight_args(segs, dY: torch.Tensor, dW_packed, dbias=None, dcbias
         if tuple(dW.shape) != tuple(s.W.shape):
             raise capi.LdmError(f"conv1d_bwd_weight seg {i}: the packed gradient must have the "
                                 f"packed weight's shape {tuple(s.W.shape)}")
-        _bwd_seg(a.seg[i], s, i, B, Cout, L_out, "conv1d_bwd_weight")
+        _fill_seg(a.seg[i], s, i, B, Cout, L_out, "conv1d_bwd_weight")
         a.dW[i] = dW.data_ptr() + s.c_off * 4
     a.dY, a.dbias, a.dcbias = dY.data_ptr(), capi.ptr(dbias), capi.ptr(dcbias)
     return a

@@ -1,10 +1,14 @@
 """C17: 1D-UNet eps-denoiser over a latent code seen as a 1-channel signal (config 5:
 1024-d latents).  Architecture: DESIGN.md §9 (the same network as ``oracle/ref_unet.py``).
 
-Every conv runs in ``ldm_conv1d`` (``csrc/unet.hip``); a reverse step is 18 launches:
+Every conv runs in ``ldm_conv1d`` (``csrc/unet.hip``); a forward is 18 launches:
 
     conv_in | Res_0 (2) | down0 | Res_1 (2) | down1 | Res_2 (2) | Res_3 (2) | up1 |
     Res_4 (2, concat as two segments) | up0 | Res_5 (2) | conv_out + DDPM step (A8)
+
+``unet_plan`` (records of buffer and weight NAMES) and ``unet_shapes`` are the only description
+of that network: ``bind_plan`` turns them into ``ConvArgs`` (the sampler per step, the trainer
+once), ``backward_schedule`` reverses the plan by name, buffers and ``step_cost`` derive from both.
 
 The timestep-embedding MLP and each block's projection are tabulated for all t once per
 weight version (``E_i[t] = P_i temb(t) + b1_i``, fp32 ``[T, Cout_i]``), so a sampling step
@@ -16,8 +20,11 @@ walks them in reverse through ``ldm_conv1d_bwd_weight`` / ``ldm_conv1d_bwd_data`
 """
 from __future__ import annotations
 
+import ctypes
+import functools
 import math
-from typing import Dict, List, Optional, Tuple
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -37,6 +44,157 @@ def is_linear_weight(name: str) -> bool:
     return name.startswith("W") or name.endswith(".p")
 
 
+def unet_res_specs(C: Tuple[int, int, int]) -> List[Tuple[int, int]]:
+    """(cin, cout) of the six residual blocks in execution order."""
+    c0, c1, c2 = C
+    return [(c0, c0), (c1, c1), (c2, c2), (c2, c2), (2 * c1, c1), (2 * c0, c0)]
+
+
+# ------------------------------------------------------------------------------- the plan
+@dataclass(frozen=True)
+class Seg:
+    """One operand of a conv: input buffer, weight, the operand's ordinal among those that read
+    this weight (> 0: a later operand of a concat weight), tap geometry, SiLU on the input."""
+    x: str
+    w: str
+    ordinal: int = 0
+    stride: int = 1
+    mode: int = capi.CONV_DIRECT
+    silu: bool = False
+    ksize: int = 3
+
+
+@dataclass(frozen=True)
+class ConvRec:
+    """One ``ldm_conv1d`` launch: output buffer, operands, bias names, the residual block whose
+    projection supplies the per-channel bias (``cb``) and the identity-residual buffer."""
+    out: str
+    segs: Tuple[Seg, ...]
+    bias: Optional[str] = None
+    bias2: Optional[str] = None
+    cb: Optional[int] = None
+    R: Optional[str] = None
+
+
+@functools.lru_cache(maxsize=None)
+def unet_plan(C: Tuple[int, int, int], fused_concat: bool = False) -> Tuple[ConvRec, ...]:
+    """The 18 convs in launch order.  ``fused_concat``: the sampler's ``n == 1`` form, where
+    res4 / res5 read the skip concat ``[u || s]`` as ONE buffer ``cat1`` / ``cat0`` whose halves
+    the producers wrote (one staging segment fewer in their two convs)."""
+    P: List[ConvRec] = []
+
+    def conv(out, x, w, **geom):
+        P.append(ConvRec(out, (Seg(x, w + ".w", **geom),), bias=w + ".b"))
+
+    def res(i, xin, a, y):
+        P.append(ConvRec(a, tuple(Seg(xi, f"res{i}.w1", k, silu=True)
+                                  for k, xi in enumerate(xin)), cb=i))
+        main = Seg(a, f"res{i}.w2", silu=True)
+        ci, co = unet_res_specs(C)[i]
+        if ci != co:            # 1x1 shortcut: further segments of the second conv
+            short = tuple(Seg(xi, f"res{i}.ws", k, ksize=1) for k, xi in enumerate(xin))
+            P.append(ConvRec(y, (main,) + short, bias=f"res{i}.b2", bias2=f"res{i}.bs"))
+        else:
+            P.append(ConvRec(y, (main,), bias=f"res{i}.b2", R=xin[0]))
+
+    conv("h0", "x", "conv_in")
+    res(0, ["h0"], "a0", "s0")
+    conv("d0", "s0", "down0", stride=2)
+    res(1, ["d0"], "a1", "s1")
+    conv("d1", "s1", "down1", stride=2)
+    res(2, ["d1"], "a2", "m0")
+    res(3, ["m0"], "a3", "m1")
+    conv("u1", "m1", "up1", mode=capi.CONV_UP2)
+    res(4, ["cat1"] if fused_concat else ["u1", "s1"], "a4", "r4")
+    conv("u0", "r4", "up0", mode=capi.CONV_UP2)
+    res(5, ["cat0"] if fused_concat else ["u0", "s0"], "a5", "r5")
+    conv("eps", "r5", "conv_out", silu=True)
+    return tuple(P)
+
+
+def unet_shapes(D: int, C: Tuple[int, int, int]) -> Dict[str, Tuple[int, int]]:
+    """(channels, length) of every buffer a plan names (``cat*``: the fused form's concats)."""
+    c0, c1, c2 = C
+    l0, l1, l2 = (c0, D), (c1, D // 2), (c2, D // 4)
+    groups = ((("x",), (1, D)), (("h0", "a0", "s0"), l0), (("d0", "a1", "s1"), l1),
+              (("d1", "a2", "m0", "a3", "m1"), l2), (("u1", "a4", "r4"), l1),
+              (("u0", "a5", "r5"), l0), (("eps",), (1, D)),
+              (("cat1",), (2 * c1, D // 2)), (("cat0",), (2 * c0, D)))
+    return {n: s for names, s in groups for n in names}
+
+
+# The two layouts of a concat conv's weight: where an operand's input channels start, given the
+# channel counts of the operands before it.
+def sample_c_off(before: Sequence[int]) -> int:
+    """``device_pack``: ``pack_conv_weight`` of the WHOLE weight.  ``conv1d_args`` rejects a start
+    that is no multiple of 16 (ragged widths at n > 1; the n == 1 fused form has one operand)."""
+    return sum(before)
+
+
+def train_c_off(before: Sequence[int]) -> int:
+    """``UNet1DDenoiser.pack_train``: each operand packed on its own, padded to 16 channels."""
+    return sum(ops._r16(c) for c in before)
+
+
+def bind_segments(rec: ConvRec, weights, bufs, c_off: Callable) -> List[ops.ConvSegment]:
+    """The ``ConvSegment`` list of one record over named weights and buffers."""
+    out = []
+    for s in rec.segs:
+        off = 0
+        if s.ordinal:
+            off = c_off([bufs[o.x].shape[1] for o in rec.segs
+                         if o.w == s.w and o.ordinal < s.ordinal])
+        out.append(ops.ConvSegment(bufs[s.x], weights[s.w], c_off=off, stride=s.stride,
+                                   mode=s.mode, silu=s.silu))
+    return out
+
+
+def bind_plan(plan: Sequence[ConvRec], weights, bufs, cbias: Callable, c_off: Callable,
+              ddpm: Optional[dict] = None) -> List[capi.ConvArgs]:
+    """A plan -> the ``ldm_conv1d`` argument structs.  ``cbias(i)`` gives block i's per-channel
+    bias tensor and its batch stride ``scb``; ``ddpm`` (``xlat``, ``z``, ``sched``, ``t``) puts
+    the A8 reverse step into the last conv's epilogue."""
+    calls = []
+    for r in plan:
+        kw = {}
+        if r.cb is not None:
+            kw["cbias"], kw["scb"] = cbias(r.cb)
+        if ddpm is not None and r is plan[-1]:
+            kw.update(ddpm, epi=capi.CONV_EPI_DDPM)
+        calls.append(ops.conv1d_args(                       # an absent name stays None
+            bind_segments(r, weights, bufs, c_off), bufs[r.out], bias=r.bias and weights[r.bias],
+            bias2=r.bias2 and weights[r.bias2], R=r.R and bufs[r.R], **kw))
+    return calls
+
+
+def backward_schedule(plan: Sequence[ConvRec]) -> List[tuple]:
+    """The backward of a plan, by name: the convs in reverse, each as
+
+        ("w", k, dbias, cb)       weight gradient of conv k: bias gradient name, block of dcbias
+        ("copy", bias2, bias)     the shortcut's bias shares the output: same sums
+        ("alias", R, out)         identity residual: R's gradient STARTS as out's (one buffer)
+        ("d", k, j, accumulate)   data gradient of segment j of conv k; an activation's gradient
+                                  is written by its first consumer here, accumulated by the later
+    The network input ``x`` gets no data gradient."""
+    sched: List[tuple] = []
+    have = {plan[-1].out}
+    for k, r in reversed(list(enumerate(plan))):
+        sched.append(("w", k, r.bias if r.cb is None else f"res{r.cb}.b1", r.cb))
+        if r.bias2 is not None:
+            sched.append(("copy", r.bias2, r.bias))
+        if r.R is not None:
+            if r.R in have:
+                raise capi.LdmError("UNetTrainer: identity residual after another consumer")
+            have.add(r.R)
+            sched.append(("alias", r.R, r.out))
+        for j, s in enumerate(r.segs):
+            if s.x == "x":
+                continue
+            sched.append(("d", k, j, s.x in have))
+            have.add(s.x)
+    return sched
+
+
 def make_work(masters: Dict[str, torch.Tensor], dtype: str) -> Dict[str, torch.Tensor]:
     """The weights the kernels read: the fp32 masters themselves, or bf16 copies (RNE) of every
     conv / linear weight with the fp32 biases."""
@@ -46,12 +204,6 @@ def make_work(masters: Dict[str, torch.Tensor], dtype: str) -> Dict[str, torch.T
         raise capi.LdmError(f"UNet training dtype {dtype!r} (fp32 | bf16)")
     return {n: v.to(torch.bfloat16) if is_conv_weight(n) or is_linear_weight(n) else v
             for n, v in masters.items()}
-
-
-def unet_res_specs(C: Tuple[int, int, int]) -> List[Tuple[int, int]]:
-    """(cin, cout) of the six residual blocks in execution order."""
-    c0, c1, c2 = C
-    return [(c0, c0), (c1, c1), (c2, c2), (c2, c2), (2 * c1, c1), (2 * c0, c0)]
 
 
 class UNet1DDenoiser:
@@ -74,6 +226,7 @@ class UNet1DDenoiser:
                        for k, v in params.items()}
         self.emb_table = torch.from_numpy(timestep_embedding_table(T, TE))
         self._dev: Dict[Tuple[str, torch.device], Dict[str, object]] = {}
+        self._trainers: Dict[tuple, "UNetTrainer"] = {}
 
     def _init(self, seed: int) -> Dict[str, torch.Tensor]:
         g = torch.Generator().manual_seed(seed)
@@ -106,51 +259,28 @@ class UNet1DDenoiser:
     def n_params(self) -> int:
         return sum(v.numel() for v in self.params.values())
 
-    def conv_list(self) -> List[Tuple[str, int, int, int, int, int, bool]]:
-        """The 18 convs of one forward, in launch order: (name, cin (all segments, the 1x1
-        shortcut's included as k=1 taps below), cout, k, L_in, L_out, identity residual)."""
-        c0, c1, c2 = self.C
-        D = self.D
-        out = [("conv_in", 1, c0, 3, D, D, False)]
-        lv = {0: (c0, D), 1: (c1, D // 2), 2: (c2, D // 4), 3: (c2, D // 4), 4: (c1, D // 2),
-              5: (c0, D)}
-
-        def res(i):
-            ci, co = unet_res_specs(self.C)[i]
-            L = lv[i][1]
-            out.append((f"res{i}.w1", ci, co, 3, L, L, False))
-            out.append((f"res{i}.w2", co, co, 3, L, L, ci == co))
-            if ci != co:
-                out.append((f"res{i}.ws", ci, co, 1, L, L, False))
-        res(0)
-        out.append(("down0", c0, c1, 3, D, D // 2, False))
-        res(1)
-        out.append(("down1", c1, c2, 3, D // 2, D // 4, False))
-        res(2)
-        res(3)
-        out.append(("up1", c2, c1, 3, D // 4, D // 2, False))
-        res(4)
-        out.append(("up0", c1, c0, 3, D // 2, D, False))
-        res(5)
-        out.append(("conv_out", c0, 1, 3, D, D, False))
-        return out
-
     def step_cost(self, n: int, weight_bytes: int = 2) -> Dict[str, float]:
         """Algorithmic work of one reverse step at batch ``n`` (bench.py config5.unet_roofline):
         FLOPs = 2 n Cout L_out Cin k summed over the convs (the 1x1 shortcuts are segments of
         their block's second conv: 18 launches); bytes = every weight once (``weight_bytes`` per
         element) + every fp32 activation a conv reads (input window, identity residual) and
         writes, + the latent in / out of the step."""
-        flops = 0
-        wbytes = 0
-        abytes = 0
-        for (_, ci, co, k, Lin, Lout, ident) in self.conv_list():
-            flops += 2 * n * co * Lout * ci * k
-            wbytes += weight_bytes * co * ci * k
-            abytes += 4 * n * (ci * Lin + co * Lout + (co * Lout if ident else 0))
+        sh = unet_shapes(self.D, self.C)
+        plan = unet_plan(self.C)
+        flops = wbytes = abytes = 0
+        for r in plan:
+            co, Lout = sh[r.out]
+            for s in r.segs:
+                ci, Lin = sh[s.x]
+                flops += 2 * n * co * Lout * ci * s.ksize
+                wbytes += weight_bytes * co * ci * s.ksize
+                # the output write is counted once per weight: a 1x1 shortcut as its own conv
+                abytes += 4 * n * (ci * Lin + (0 if s.ordinal else co * Lout))
+            if r.R is not None:
+                abytes += 4 * n * co * Lout
         return {"flops": float(flops), "bytes": float(wbytes + abytes),
                 "weight_bytes": float(wbytes), "activation_bytes": float(abytes),
-                "launches": 18}
+                "launches": len(plan)}
 
     def invalidate(self) -> None:
         self._dev.clear()
@@ -162,8 +292,11 @@ class UNet1DDenoiser:
 
     def _first_half(self, name: str) -> Optional[int]:
         """Channels of the first operand of a decoder-side concat conv ([u || s]), else None."""
-        c0, c1, _ = self.C
-        return {"res4.w1": c1, "res4.ws": c1, "res5.w1": c0, "res5.ws": c0}.get(name)
+        for r in unet_plan(self.C):
+            xs = [s.x for s in r.segs if s.w == name]
+            if len(xs) > 1:
+                return unet_shapes(self.D, self.C)[xs[0]][0]
+        return None
 
     def pack_train(self, name: str, v: torch.Tensor) -> torch.Tensor:
         """Torch layout -> training layout (device tensors): conv weights packed for the matrix
@@ -205,12 +338,10 @@ class UNet1DDenoiser:
         """A cached trainer over ``params`` as they were when it was built (``api.train_step``);
         ``invalidate()`` drops it, as it drops the sampling packs."""
         key = (dtype, torch.device(device), B)
-        tr = getattr(self, "_trainers", {})
-        if key not in tr:
+        if key not in self._trainers:
             masters = self.train_masters(device)
-            tr[key] = UNetTrainer(self, masters, make_work(masters, dtype), B, device)
-            self._trainers = tr
-        return tr[key]
+            self._trainers[key] = UNetTrainer(self, masters, make_work(masters, dtype), B, device)
+        return self._trainers[key]
 
     # ------------------------------------------------------------------------- device pack
     def device_pack(self, dtype: str, device) -> Dict[str, object]:
@@ -224,9 +355,9 @@ class UNet1DDenoiser:
         dev: Dict[str, object] = {}
         for n, v in self.params.items():
             v = v.to(device)
-            if n.endswith((".w", ".w1", ".w2", ".ws")):        # conv: matrix-core packing
+            if is_conv_weight(n):         # matrix-core packing of the whole weight (sample_c_off)
                 dev[n] = ops.pack_conv_weight(v.to(wdt))
-            elif n.startswith("W") or n.endswith(".p"):       # linear [out][in]
+            elif is_linear_weight(n):     # [out][in]
                 dev[n] = v.to(wdt).contiguous()
             else:
                 dev[n] = v.to(torch.float32).contiguous()
@@ -241,22 +372,17 @@ class UNet1DDenoiser:
 
     # ------------------------------------------------------------------------- forward
     def buffers(self, n: int, device) -> Dict[str, torch.Tensor]:
-        """Activation buffers for a batch of ``n`` (allocated once per sampler)."""
-        c0, c1, c2 = self.C
-        D = self.D
-        f = lambda *s: torch.empty(*s, device=device, dtype=torch.float32)  # noqa: E731
-        b = {"h0": f(n, c0, D), "a0": f(n, c0, D), "s0": f(n, c0, D),
-             "d0": f(n, c1, D // 2), "a1": f(n, c1, D // 2), "s1": f(n, c1, D // 2),
-             "d1": f(n, c2, D // 4), "a2": f(n, c2, D // 4), "m0": f(n, c2, D // 4),
-             "m1": f(n, c2, D // 4), "u1": f(n, c1, D // 2), "a4": f(n, c1, D // 2),
-             "r4": f(n, c1, D // 2), "u0": f(n, c0, D), "a5": f(n, c0, D),
-             "r5": f(n, c0, D), "eps": f(n, 1, D)}
+        """Activation buffers for a batch of ``n`` (allocated once per sampler), by plan name;
+        ``a3`` is ``a2`` again (nothing reads res2's inner activation after res3 starts)."""
+        sh = unet_shapes(self.D, self.C)
+        f = lambda name: torch.empty(n, *sh[name], device=device, dtype=torch.float32)  # noqa
+        b = {name: f(name) for name in sh if name not in ("x", "a3", "cat1", "cat0")}
+        b["a3"] = b["a2"]
         if n == 1:
             # the decoder-side skip concats [u || s] as ONE buffer whose halves the producers
-            # write: res4 / res5 then read it as one segment (one staging segment fewer in
-            # their two convs, DESIGN.md §9); a channel slice is contiguous only at n = 1
-            for lvl, c in ((1, c1), (0, c0)):
-                cat = f(1, 2 * c, D >> lvl)
+            # write (unet_plan's fused_concat); a channel slice is contiguous only at n = 1
+            for lvl in (1, 0):
+                cat, c = f(f"cat{lvl}"), sh[f"u{lvl}"][0]
                 b[f"cat{lvl}"], b[f"u{lvl}"], b[f"s{lvl}"] = cat, cat[:, :c], cat[:, c:]
         return b
 
@@ -268,58 +394,12 @@ class UNet1DDenoiser:
         With ``sched`` the last call writes the A8 reverse step ``x_{t-1}`` into ``out``
         ([n, D]); without, it writes eps_hat.  ``cbias`` overrides the tabulated per-block
         bias rows (training: per-sample ``[n, Cout_i]``)."""
-        S = ops.ConvSegment
-        UP2 = capi.CONV_UP2
         n = x.shape[0]
-        calls: List[capi.ConvArgs] = []
-
-        def cb(i):
-            if cbias is not None:
-                return dict(cbias=cbias[i], scb=cbias[i].shape[1])
-            return dict(cbias=dev[f"etab{i}"][t], scb=0)
-
-        def res(i, xin: List[torch.Tensor], a, y):
-            w1, w2 = dev[f"res{i}.w1"], dev[f"res{i}.w2"]
-            segs, off = [], 0
-            for xi in xin:
-                segs.append(S(xi, w1, c_off=off, silu=True))
-                off += xi.shape[1]
-            calls.append(ops.conv1d_args(segs, a, **cb(i)))
-            segs2 = [S(a, w2, silu=True)]
-            if f"res{i}.ws" in dev:
-                ws, off = dev[f"res{i}.ws"], 0
-                for xi in xin:
-                    segs2.append(S(xi, ws, c_off=off))
-                    off += xi.shape[1]
-                calls.append(ops.conv1d_args(segs2, y, bias=dev[f"res{i}.b2"],
-                                             bias2=dev[f"res{i}.bs"]))
-            else:
-                calls.append(ops.conv1d_args(segs2, y, bias=dev[f"res{i}.b2"], R=xin[0]))
-
-        b = buf
-        x3 = x.view(n, 1, self.D)
-        calls.append(ops.conv1d_args([S(x3, dev["conv_in.w"])], b["h0"], bias=dev["conv_in.b"]))
-        res(0, [b["h0"]], b["a0"], b["s0"])
-        calls.append(ops.conv1d_args([S(b["s0"], dev["down0.w"], stride=2)], b["d0"],
-                                     bias=dev["down0.b"]))
-        res(1, [b["d0"]], b["a1"], b["s1"])
-        calls.append(ops.conv1d_args([S(b["s1"], dev["down1.w"], stride=2)], b["d1"],
-                                     bias=dev["down1.b"]))
-        res(2, [b["d1"]], b["a2"], b["m0"])
-        res(3, [b["m0"]], b["a2"], b["m1"])
-        calls.append(ops.conv1d_args([S(b["m1"], dev["up1.w"], mode=UP2)], b["u1"],
-                                     bias=dev["up1.b"]))
-        res(4, [b["cat1"]] if "cat1" in b else [b["u1"], b["s1"]], b["a4"], b["r4"])
-        calls.append(ops.conv1d_args([S(b["r4"], dev["up0.w"], mode=UP2)], b["u0"],
-                                     bias=dev["up0.b"]))
-        res(5, [b["cat0"]] if "cat0" in b else [b["u0"], b["s0"]], b["a5"], b["r5"])
-        last = [S(b["r5"], dev["conv_out.w"], silu=True)]
-        if sched is not None:
-            calls.append(ops.conv1d_args(last, out.view(n, 1, self.D), bias=dev["conv_out.b"],
-                                         epi=capi.CONV_EPI_DDPM, xlat=x, z=z, sched=sched, t=t))
-        else:
-            calls.append(ops.conv1d_args(last, out.view(n, 1, self.D), bias=dev["conv_out.b"]))
-        return calls
+        bufs = {**buf, "x": x.view(n, 1, self.D), "eps": out.view(n, 1, self.D)}
+        cb = ((lambda i: (dev[f"etab{i}"][t], 0)) if cbias is None else
+              (lambda i: (cbias[i], cbias[i].shape[1])))
+        ddpm = None if sched is None else dict(xlat=x, z=z, sched=sched, t=t)
+        return bind_plan(unet_plan(self.C, "cat1" in buf), dev, bufs, cb, sample_c_off, ddpm)
 
     def forward_uniform_t(self, x: torch.Tensor, t: int, dtype: str = "bf16") -> torch.Tensor:
         """eps_hat = UNet(x, t) for a batch sharing one timestep (device tensors)."""
@@ -358,112 +438,50 @@ class UNetTrainer:
     def __init__(self, model: UNet1DDenoiser, masters, work, B: int, device):
         self.model, self.masters, self.work, self.B = model, masters, work, B
         self.device = device = torch.device(device)
-        c0, c1, c2 = model.C
-        D = model.D
         f = lambda *s: torch.empty(*s, device=device, dtype=torch.float32)  # noqa: E731
-        shapes = {"x": (1, D), "h0": (c0, D), "a0": (c0, D), "s0": (c0, D),
-                  "d0": (c1, D // 2), "a1": (c1, D // 2), "s1": (c1, D // 2),
-                  "d1": (c2, D // 4), "a2": (c2, D // 4), "m0": (c2, D // 4),
-                  "a3": (c2, D // 4), "m1": (c2, D // 4), "u1": (c1, D // 2),
-                  "a4": (c1, D // 2), "r4": (c1, D // 2), "u0": (c0, D), "a5": (c0, D),
-                  "r5": (c0, D), "eps": (1, D)}
+        self.plan = unet_plan(model.C)
+        used = {s.x for r in self.plan for s in r.segs} | {r.out for r in self.plan}
         # every activation the backward needs is kept (the sampler reuses a2 for res2 / res3)
-        self.act = {n: f(B, *s) for n, s in shapes.items()}
+        self.act = {n: f(B, *s) for n, s in unet_shapes(model.D, model.C).items() if n in used}
         self.grads = {n: torch.zeros_like(v) for n, v in masters.items()}
         specs = unet_res_specs(model.C)
         self.cb = [f(B, co) for _, co in specs]
         self.dcb = [f(B, co) for _, co in specs]
-        self.loss = f(1)
         self.dtemb, self.du = f(B, model.HT), f(B, model.HT)
         self.emb = model.emb_table.to(device).contiguous()
-        self._build()
+        self.fwd = bind_plan(self.plan, work, self.act,
+                             lambda i: (self.cb[i], self.cb[i].shape[1]), train_c_off)
+        self._bind_backward()
 
-    def plan(self) -> List[dict]:
-        """The 18 convs in launch order: output buffer, segments (input buffer, weight, channel
-        offset, stride, mode, SiLU), biases, the block whose projection is the per-sample
-        bias, and the identity residual."""
-        UP2 = capi.CONV_UP2
-        P: List[dict] = []
-
-        def conv(out, segs, bias=None, bias2=None, cb=None, R=None):
-            P.append(dict(out=out, segs=segs, bias=bias, bias2=bias2, cb=cb, R=R))
-
-        def res(i, xin, a, y):
-            segs, off = [], 0
-            for xi in xin:
-                segs.append((xi, f"res{i}.w1", off, 1, 0, True))
-                off += ops._r16(self.act[xi].shape[1])      # UNet1DDenoiser.pack_train
-            conv(a, segs, cb=i)
-            segs2 = [(a, f"res{i}.w2", 0, 1, 0, True)]
-            if f"res{i}.ws" in self.masters:
-                off = 0
-                for xi in xin:
-                    segs2.append((xi, f"res{i}.ws", off, 1, 0, False))
-                    off += ops._r16(self.act[xi].shape[1])
-                conv(y, segs2, bias=f"res{i}.b2", bias2=f"res{i}.bs")
-            else:
-                conv(y, segs2, bias=f"res{i}.b2", R=xin[0])
-
-        conv("h0", [("x", "conv_in.w", 0, 1, 0, False)], bias="conv_in.b")
-        res(0, ["h0"], "a0", "s0")
-        conv("d0", [("s0", "down0.w", 0, 2, 0, False)], bias="down0.b")
-        res(1, ["d0"], "a1", "s1")
-        conv("d1", [("s1", "down1.w", 0, 2, 0, False)], bias="down1.b")
-        res(2, ["d1"], "a2", "m0")
-        res(3, ["m0"], "a3", "m1")
-        conv("u1", [("m1", "up1.w", 0, 1, UP2, False)], bias="up1.b")
-        res(4, ["u1", "s1"], "a4", "r4")
-        conv("u0", [("r4", "up0.w", 0, 1, UP2, False)], bias="up0.b")
-        res(5, ["u0", "s0"], "a5", "r5")
-        conv("eps", [("r5", "conv_out.w", 0, 1, 0, True)], bias="conv_out.b")
-        return P
-
-    def _build(self) -> None:
-        S = ops.ConvSegment
-        act, work, grads = self.act, self.work, self.grads
-        self.fwd: List[capi.ConvArgs] = []
-        recs = []
-        for r in self.plan():
-            segs = [S(act[xi], work[w], c_off=off, stride=st, mode=mode, silu=silu)
-                    for (xi, w, off, st, mode, silu) in r["segs"]]
-            kw = {}
-            if r["cb"] is not None:
-                kw = dict(cbias=self.cb[r["cb"]], scb=self.cb[r["cb"]].shape[1])
-            self.fwd.append(ops.conv1d_args(
-                segs, act[r["out"]], bias=None if r["bias"] is None else work[r["bias"]],
-                bias2=None if r["bias2"] is None else work[r["bias2"]],
-                R=None if r["R"] is None else act[r["R"]], **kw))
-            recs.append((r, segs))
-        # the backward: convs in reverse; an activation's gradient buffer is written by its
-        # first consumer (in this order) and accumulated by the later ones; an identity
-        # residual makes the block input's gradient START as the block output's (one buffer)
+    def _bind_backward(self) -> None:
+        """``backward_schedule`` over tensors: the argument structs in launch order (``bwd``),
+        the bias copies, one gradient buffer per activation (``G``) and the workspace."""
+        plan, act, grads = self.plan, self.act, self.grads
+        segs = [bind_segments(r, self.work, act, train_c_off) for r in plan]
         G: Dict[str, torch.Tensor] = {"eps": torch.empty_like(act["eps"])}
         self.g_eps = G["eps"]
         self.bwd: List[tuple] = []
         self.copies: List[tuple] = []
         ws_need = 1
-        for r, segs in reversed(recs):
-            dY = G[r["out"]]
-            i = r["cb"]
-            wa = ops.conv1d_bwd_weight_args(
-                segs, dY, [grads[w] for (_, w, *_r) in r["segs"]],
-                dbias=grads[f"res{i}.b1"] if i is not None else grads[r["bias"]],
-                dcbias=self.dcb[i] if i is not None else None)
-            ws_need = max(ws_need, ops.conv1d_bwd_weight_ws_floats(wa))
-            self.bwd.append(("w", wa))
-            if r["bias2"] is not None:       # the shortcut's bias shares the output: same sums
-                self.copies.append((grads[r["bias2"]], grads[r["bias"]]))
-            if r["R"] is not None:
-                if r["R"] in G:
-                    raise capi.LdmError("UNetTrainer: identity residual after another consumer")
-                G[r["R"]] = dY
-            for seg, (xi, *_r) in zip(segs, r["segs"]):
-                if xi == "x":
-                    continue                 # conv_in needs no data gradient
-                accumulate = xi in G
+        for kind, *e in backward_schedule(plan):
+            if kind == "w":
+                k, dbias, cb = e
+                wa = ops.conv1d_bwd_weight_args(
+                    segs[k], G[plan[k].out], [grads[s.w] for s in plan[k].segs],
+                    dbias=grads[dbias], dcbias=None if cb is None else self.dcb[cb])
+                ws_need = max(ws_need, ops.conv1d_bwd_weight_ws_floats(wa))
+                self.bwd.append(("w", wa))
+            elif kind == "copy":
+                self.copies.append((grads[e[0]], grads[e[1]]))
+            elif kind == "alias":
+                G[e[0]] = G[e[1]]
+            else:
+                k, j, accumulate = e
+                x = plan[k].segs[j].x
                 if not accumulate:
-                    G[xi] = torch.empty_like(act[xi])
-                self.bwd.append(("d", ops.conv1d_bwd_data_args(seg, dY, G[xi], accumulate)))
+                    G[x] = torch.empty_like(act[x])
+                self.bwd.append(("d", ops.conv1d_bwd_data_args(segs[k][j], G[plan[k].out], G[x],
+                                                               accumulate)))
         self.G = G
         self.ws = torch.empty(ws_need, device=self.device, dtype=torch.float32)
         for kind, a in self.bwd:
@@ -473,7 +491,6 @@ class UNetTrainer:
     def step(self, sched_desc, x0: torch.Tensor, t: torch.Tensor, eps: torch.Tensor
              ) -> torch.Tensor:
         """q_sample -> forward -> eps-MSE -> every gradient (into ``grads``); the loss [1]."""
-        import ctypes as C
         m, work, grads, B = self.model, self.work, self.grads, self.B
         capi.require_device(x0, t, eps)
         if tuple(x0.shape) != (B, m.D) or tuple(eps.shape) != (B, m.D) or t.numel() != B:
@@ -481,7 +498,7 @@ class UNetTrainer:
         x0, eps = x0.float().contiguous(), eps.float().contiguous()
         t = t.to(torch.int32).contiguous()
         lib, st = capi.load(), capi.stream_handle(self.device)
-        capi.check(lib.ldm_q_sample(C.byref(sched_desc), x0.data_ptr(), eps.data_ptr(),
+        capi.check(lib.ldm_q_sample(ctypes.byref(sched_desc), x0.data_ptr(), eps.data_ptr(),
                                     t.data_ptr(), B, m.D, self.act["x"].data_ptr(), st),
                    "ldm_q_sample")
         sv: dict = {}
@@ -490,16 +507,16 @@ class UNetTrainer:
             ops.linear(temb, work[f"res{i}.p"], self.cb[i], epi=capi.EPI_BIAS,
                        bias=work[f"res{i}.b1"])
         for a in self.fwd:
-            capi.check(lib.ldm_conv1d(C.byref(a), st), "ldm_conv1d")
+            capi.check(lib.ldm_conv1d(ctypes.byref(a), st), "ldm_conv1d")
         loss = torch.empty(1, device=self.device, dtype=torch.float32)
         capi.check(lib.ldm_eps_mse_loss(self.act["eps"].data_ptr(), eps.data_ptr(), eps.numel(),
                                         loss.data_ptr(), self.g_eps.data_ptr(), st),
                    "ldm_eps_mse_loss")
         for kind, a in self.bwd:
             if kind == "w":
-                capi.check(lib.ldm_conv1d_bwd_weight(C.byref(a), st), "ldm_conv1d_bwd_weight")
+                capi.check(lib.ldm_conv1d_bwd_weight(ctypes.byref(a), st), "ldm_conv1d_bwd_weight")
             else:
-                capi.check(lib.ldm_conv1d_bwd_data(C.byref(a), st), "ldm_conv1d_bwd_data")
+                capi.check(lib.ldm_conv1d_bwd_data(ctypes.byref(a), st), "ldm_conv1d_bwd_data")
         for dst, src in self.copies:
             dst.copy_(src)
         # cbias_i = P_i temb + b1_i: dP_i = dcb_i^T temb, dtemb = sum_i dcb_i P_i (block order)
