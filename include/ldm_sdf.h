@@ -664,6 +664,32 @@ int ldm_mc_emit(const float* vol, int N, float level, float vs, float origin, vo
  * coordinate bits (lower axis first) are m; corner c sits at (c & 1, c >> 1 & 1, c >> 2 & 1). */
 int ldm_mc_table(int8_t* tri, uint8_t* ntri);
 
+/* ---- mesh -> signed distance samples (additive in ABI 7) ------------------ */
+/* For P points [P][3] against the triangle soup verts fp32 [V][3], faces int32 [F][3], every
+ * point-triangle pair evaluated:
+ *   sdf      [P]  -d when winding > 0.5, else +d; d the distance to the closest triangle
+ *                 (Voronoi-region closest point; a zero-area triangle is its segment or point)
+ *   closest  [P]  (or NULL) index of that triangle, the smaller index on a tie
+ *   winding  [P]  (or NULL) generalized winding number, sum of solid angles / 4 pi (a pair
+ *                 whose triple product is exactly 0 contributes 0)
+ * A point's outputs are a pure function of the point and the mesh: bitwise the same alone or
+ * in any batch, and from run to run.  F == 0 gives d = +inf, closest = -1, winding = 0; P == 0
+ * returns 0 with nothing written.
+ * A face index outside [0, V) is never read through: it is clamped, and the device word *flag
+ * (zeroed by the call) is set to 1 -- the outputs are then meaningless.
+ * ws: 256-byte aligned, ldm_mesh_sdf_ws_bytes(F, P) bytes (0 for negative sizes); it holds the
+ * packed triangles and, below ldm_mesh_sdf_split_below() points with more than one chunk of
+ * ldm_mesh_sdf_face_chunk() faces, one tile of per-chunk partials.
+ * LDM_EINVAL also for a grid beyond the launch limits: more than 65535 chunks of faces in the
+ * split form, more than 2^31 - 1 workgroups of 256 points in the other. */
+size_t ldm_mesh_sdf_ws_bytes(int F, int64_t P);
+int ldm_mesh_sdf(const float* verts, int V, const int32_t* faces, int F, const float* points,
+                 int64_t P, float* sdf, int32_t* closest, float* winding, int32_t* flag,
+                 void* ws, size_t ws_bytes, ldm_stream_t s);
+/* Host: the two constants of the summation shape and the launch form. */
+int ldm_mesh_sdf_face_chunk(void);
+int64_t ldm_mesh_sdf_split_below(void);
+
 #ifdef __cplusplus
 }
 #endif

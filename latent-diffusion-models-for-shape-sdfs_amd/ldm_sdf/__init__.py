@@ -8,7 +8,7 @@ over ``torch.distributed`` (RCCL).
 from .models import DDPMSchedule, MLPDenoiser, SDFDecoder, decoder_layer_dims  # noqa: F401
 from .unet import UNet1DDenoiser  # noqa: F401
 from .mesh import (marching_cubes, marching_cubes_batch, mc_table, vertex_normals,  # noqa: F401
-                   write_ply)
+                   write_ply, read_ply, read_obj)
 from .api import (Sampler, TrainState, decode, decode_points, resolve_decode_dtype,  # noqa: F401
                   sample, train, train_step)
 from .band import (BandInfo, decode_band, extract_mesh, lattice_indices,  # noqa: F401
@@ -16,7 +16,8 @@ from .band import (BandInfo, decode_band, extract_mesh, lattice_indices,  # noqa
 from .autodecoder import (AutoDecoderState, autodecoder_train_step,  # noqa: F401
                           train_autodecoder)
 from .grad import fit_latents, sdf_grad  # noqa: F401
-from . import ops, dist, pack, data  # noqa: F401
+from .meshsdf import mesh_sdf, normalize_mesh, sample_sdf, sample_surface  # noqa: F401
+from . import ops, dist, pack, data, meshsdf  # noqa: F401
 from ._capi import LdmError, load as load_library  # noqa: F401
 
 __version__ = "0.1.0"

@@ -231,6 +231,10 @@ SIGNATURES = [
     ("ldm_mc_count", _i, [_fp, _i, _f, _vp, _sz, _vp, _vp]),
     ("ldm_mc_emit", _i, [_fp, _i, _f, _f, _f, _vp, _sz, _fp, _vp, _vp]),
     ("ldm_mc_table", _i, [_vp, _vp]),
+    ("ldm_mesh_sdf_ws_bytes", _sz, [_i, C.c_int64]),
+    ("ldm_mesh_sdf", _i, [_fp, _i, _vp, _i, _fp, C.c_int64, _fp, _vp, _fp, _vp, _vp, _sz, _vp]),
+    ("ldm_mesh_sdf_face_chunk", _i, []),
+    ("ldm_mesh_sdf_split_below", C.c_int64, []),
 ]
 
 _lib: Optional[C.CDLL] = None

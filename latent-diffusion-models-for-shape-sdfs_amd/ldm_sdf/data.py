@@ -27,7 +27,7 @@ import torch
 
 from .models import SDFDecoder
 
-__all__ = ["load_sdf_samples", "unpack_sdf_samples", "SdfSampleSet", "save_model",
+__all__ = ["load_sdf_samples", "save_sdf_samples", "unpack_sdf_samples", "SdfSampleSet", "save_model",
            "load_model", "save_latent_codes", "load_latent_codes"]
 
 
@@ -46,6 +46,20 @@ def load_sdf_samples(path: str) -> Tuple[torch.Tensor, torch.Tensor]:
             raise ValueError(f"{path}: '{name}' must be [n, 4] (x, y, z, sdf), got {a.shape}")
     return (torch.from_numpy(_remove_nans(pos).astype(np.float32)),
             torch.from_numpy(_remove_nans(neg).astype(np.float32)))
+
+
+def save_sdf_samples(path: str, pos, neg) -> None:
+    """Write the ``.npz`` ``load_sdf_samples`` reads: ``pos`` and ``neg`` as ``[n, 4]`` float32
+    rows ``(x, y, z, sdf)``, bit for bit (tensors on any device, or arrays)."""
+    arrs = {}
+    for name, a in (("pos", pos), ("neg", neg)):
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError(f"save_sdf_samples: '{name}' must be [n, 4], got {a.shape}")
+        arrs[name] = np.ascontiguousarray(a, np.float32)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:                 # (a file object: numpy adds no suffix)
+        np.savez(fh, **arrs)
 
 
 def unpack_sdf_samples(pos: torch.Tensor, neg: torch.Tensor, subsample: int,
