@@ -1,5 +1,6 @@
 // Device helpers shared by the decoder kernels (decoder.hip, decoder_fs.hip).
 #pragma once
+#include "grid_index.h"
 #include "ldm_internal.h"
 
 #include <math.h>
@@ -56,6 +57,16 @@ struct Elem<__bf16> {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
                                                        __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
     }
+    // a * b (C = 0) into VGPRs.  The builtin cannot say that: in a kernel that keeps
+    // accumulators in AGPRs the compiler selects the AGPR destination for every MFMA and copies
+    // the product back one register at a time.  An asm statement gets NO wait states from the
+    // compiler: the caller keeps 12 issue slots between this statement and the first reader of
+    // the product, and writes neither operand in the 2 slots before it (mfma_v's users say how).
+    static __device__ __forceinline__ f32x16 mfma_v(u32x4 a, u32x4 b) {
+        f32x16 d;
+        asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));
+        return d;
+    }
     static __device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
         return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
                                                        __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -71,6 +82,16 @@ struct Elem<_Float16> {
     static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a),
                                                       __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    }
+    // a * b (C = 0) into VGPRs.  The builtin cannot say that: in a kernel that keeps
+    // accumulators in AGPRs the compiler selects the AGPR destination for every MFMA and copies
+    // the product back one register at a time.  An asm statement gets NO wait states from the
+    // compiler: the caller keeps 12 issue slots between this statement and the first reader of
+    // the product, and writes neither operand in the 2 slots before it (mfma_v's users say how).
+    static __device__ __forceinline__ f32x16 mfma_v(u32x4 a, u32x4 b) {
+        f32x16 d;
+        asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));
+        return d;
     }
     static __device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a),

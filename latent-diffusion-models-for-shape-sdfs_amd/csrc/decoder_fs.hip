@@ -122,6 +122,7 @@ struct FArgs {
     const int32_t* bricks;   // ascending global brick ids, the first *count of them valid
     const int32_t* count;    // device count of active bricks
     int nb, nbt;             // bricks per axis, B * nb^3
+    GridDiv gd;              // grid mode: the reciprocals of N (grid_index.h)
 };
 
 // Epilogue kinds run inside 8 k-steps of a part (on the OTHER accumulator set)
@@ -262,6 +263,20 @@ __device__ __forceinline__ float relu_f(float x) {
     return __builtin_bit_cast(float, max(__builtin_bit_cast(int, x), 0));
 }
 
+// One element of the set FE_FIN1 folds, read out of the accumulator file AT ITS USE.  That set
+// is carried around the tile loop (layer 7 part 1 of the previous tile), and as a plain value
+// the register allocator split it at the loop header: 128 v_accvgpr_read there, with the matrix
+// pipe idle, and 128 VGPRs held across layer 0 (DESIGN.md §4 "tile prologue").  An EMPTY asm
+// statement with the element as an "a" operand pins it to the accumulator file up to this
+// point; the v_accvgpr_read that follows is the compiler's own, so it fills the step's VALU
+// slots and gets its wait states like any other.  (One pin of the whole set after layer 0
+// instead made the allocator shuffle 64 registers through v_accvgpr_mov / _write; a pin per
+// element at its use adds no instruction.)
+__device__ __forceinline__ float acc_read(float a) {
+    asm volatile("" : "+a"(a));
+    return a;
+}
+
 // One epilogue unit u = 2t + s of the other accumulator set: HALF of tile t = 4i + n (its
 // accumulator registers 8s..8s+7 = the B fragment of k-step 2i + s).
 template <typename T, int EK>
@@ -283,7 +298,11 @@ __device__ __forceinline__ void epi_unit(FCtx& c, const f32x16 (&accY)[2][4], in
         for (int q = 2 * s; q < 2 * s + 2; ++q) {
             const f32x4 wv = w[q];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) part = fmaf(relu_f(accY[i][n][4 * q + e]), wv[e], part);
+            for (int e = 0; e < 4; ++e) {
+                const float v = EK == FE_FIN1 ? acc_read(accY[i][n][4 * q + e])
+                                              : accY[i][n][4 * q + e];
+                part = fmaf(relu_f(v), wv[e], part);
+            }
         }
         c.part[n] = part;
     }
@@ -516,16 +535,6 @@ __device__ __forceinline__ void run_part(FCtx& c, f32x16 (&acc)[2][4], const f32
                                          bool bar0) {
     const f32x16 zero = {};
     const u32x4 a0 = c.auxn[0], a1 = c.auxn[1];
-    if (nk == 0) {             // layer 0: the aux step only, c.b stays the xyz fragments
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            acc[0][n] = Elem<T>::mfma(a0, c.b[n], zero);
-            acc[1][n] = Elem<T>::mfma(a1, c.b[n], zero);
-        }
-        load_aux(c, naux);
-        stamp(c);
-        return;
-    }
     if (bar0) {
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
@@ -557,7 +566,10 @@ __device__ __forceinline__ void run_part(FCtx& c, f32x16 (&acc)[2][4], const f32
         // the barrier inside step 15: mid (nk 32), or the end barrier of a 16-step part
         if (mid || (endbar && nk == 16)) steps16e<T, EK, true>(c, acc, accY, pos0);
         else steps16e<T, EK, false>(c, acc, accY, pos0);
-        if (EK == FE_FIN1) fin_store_mode<MODE>(c);
+        if (EK == FE_FIN1) {
+            stamp(c);
+            fin_store_mode<MODE>(c);
+        }
         stamp(c);
         if (endbar && nk == 32) {       // the end barrier inside step 31
             steps_plain<T>(c, acc, accY, pos0, 16, 28);
@@ -579,11 +591,11 @@ __device__ __forceinline__ void run_part(FCtx& c, f32x16 (&acc)[2][4], const f32
     stamp(c);
 }
 
-// a whole set into this wave's early (LATE = false) or late positions 16u + 4w + 2i + s
-// (serial: layer 0, layer 3 at skip 253); the per-wave base and immediates per tile
-template <typename T, bool LATE>
+// a whole set into this wave's late positions 16 + 4w + 2i + s (serial: layer 3 at skip 253);
+// the per-wave base and immediates per tile
+template <typename T>
 __device__ __forceinline__ void acc_to_lds(FCtx& c, const f32x16 (&acc)[2][4]) {
-    u32x4* p = act_w(c, LATE ? 16 : 0);
+    u32x4* p = act_w(c, 16);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -593,6 +605,47 @@ __device__ __forceinline__ void acc_to_lds(FCtx& c, const f32x16 (&acc)[2][4]) {
             p[(2 * i * 4 + n) * 64] = f0;
             p[((2 * i + 1) * 4 + n) * 64] = f1;
         }
+}
+
+// One part of layer 0: a single K = 16 step per tile, [wx,wy,wz,wx,wy,wz,b_hi,b_lo] x the xyz
+// fragments in c.b (which stay), straight from the matrix pipe to this wave's early (LATE =
+// false) or late positions.  The 8 products (m-chunk i, point chunk n) go through two VGPR
+// temporaries (Elem::mfma_v) instead of an accumulator set: nothing is read back from AGPRs,
+// and set B keeps the previous tile's layer 7 part 1 untouched.  Then the next part's aux A
+// fragments (naux) are loaded.
+// Wait states (mfma_v: the compiler pads nothing around an asm statement).  A 32x32x16 product is
+// an 8-pass XDL op; its D may be read by a VALU 12 issue slots after it (the CDNA3/4 ISA's table
+// of required software wait states, row "XDL write VGPR -> VALU read/write, VMEM/LDS/FLAT read:
+// 8 passes: 11", one more as the guide's margin).  Product q+1 is issued BEFORE product q is
+// converted, and the scheduling barriers pin that order:
+//     P0 P1 nop | cvt 0 | P2 | cvt 1 | P3 | ... | P7 | cvt 6 | cvt 7
+// so between P(q) and its first reader stand P(q+1) and, for q >= 1, the whole of cvt q-1 (8
+// v_cvt_pk, 8 v_pk_max, 2 ds_write); only P0 needs nops (P1 + s_nop 10 = 12 slots).  The
+// operands of a product are loaded fragments, complete long before (VALU write -> MFMA read
+// needs 2 slots); tests/test_decoder_codegen.py counts both distances in the assembly.
+template <typename T, bool LATE>
+__device__ __forceinline__ void layer0_part(FCtx& c, FSrc naux) {
+    const u32x4 a[2] = {c.auxn[0], c.auxn[1]};
+    u32x4* p = act_w(c, LATE ? 16 : 0);
+    f32x16 t[2];
+    t[0] = Elem<T>::mfma_v(a[0], c.b[0]);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int i = q & 1, n = q >> 1;
+        if (q < 7) t[(q + 1) & 1] = Elem<T>::mfma_v(a[(q + 1) & 1], c.b[(q + 1) >> 1]);
+        if (q == 0) {
+            asm volatile("s_nop 10" : "+v"(t[0]));
+            load_aux(c, naux);
+            stamp(c);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        u32x4 f0, f1;
+        acc_to_frags<T>(t[q & 1], f0, f1);
+        p[(2 * i * 4 + n) * 64] = f0;
+        p[((2 * i + 1) * 4 + n) * 64] = f1;
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    stamp(c);
 }
 
 // MODE (decoder_common.h): where a tile's points come from and its outputs go -- a run of 128
@@ -691,6 +744,23 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
         // were spilled and reloaded behind the whole weight ring)
         const uint32_t lv = opaque(c.voff);
         const bool hi = lv >= 512u;                       // lane >= 32
+        // grid mode: the tile's first voxel, once and on the scalar unit (grid_index.h; the
+        // reciprocals of N are kernel arguments: SGPRs, nothing per lane).  The per-lane
+        // divisions this replaces were 8 v_rcp_iflag sequences, ~290 VALU, a tile.
+        const uint32_t p0 = (uint32_t)local * kTilePoints;
+        uint32_t ti = 0, tj = 0, tk = 0;
+        if (MODE == kModeGrid) {
+            grid_first(p0, (uint32_t)a.N, a.gd, ti, tj, tk);
+            tk += (uint32_t)a.k0;
+        }
+        // points mode: the shape's row of the list as a scalar pointer.  Folded into the lanes'
+        // 64-bit address (shape * npts + pt as one vector mad), npts took a VGPR that was hoisted
+        // out of the tile loop and spilled; its reload here waited vmcnt(0), the whole weight ring
+        const float* row = nullptr;
+        if (MODE == kModePoints) {
+            row = a.xyz + (size_t)shape * a.npts * 3;
+            asm volatile("" : "+s"(row));
+        }
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
             int pt = local * kTilePoints + 32 * n + (int)((lv >> 4) & 31u);
@@ -704,14 +774,21 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
                 y = grid_axis(min(bj0 + ((idx >> 3) & 7), m), a.vs, a.origin);
                 z = grid_axis(min(bk0 + (idx >> 6), m), a.vs, a.origin);
             } else if (MODE == kModePoints) {
-                const float* qq = a.xyz + ((size_t)shape * a.npts + pt) * 3;
+                const float* qq = row + (size_t)pt * 3;
                 x = qq[0];
                 y = qq[1];
                 z = qq[2];
             } else {
-                // N through an opaque SGPR: the divisions' reciprocals are formed per tile
-                // instead of hoisted out of the loop (and spilled)
-                grid_point(pt, opaque_s(a.N), a.k0, a.vs, a.origin, x, y, z);
+                // the lane's voxel from the tile's first one: its offset (clamped to the slab's
+                // last point in the ragged tail: the point min(pt, npts - 1) above) and two
+                // carries, each a multiply-high by the reciprocal of N
+                const uint32_t off =
+                    grid_tail_off(p0, 32u * n + ((lv >> 4) & 31u), (uint32_t)a.npts);
+                uint32_t vi, vj, vk;
+                grid_voxel(ti, tj, tk, off, (uint32_t)a.N, a.gd.m, vi, vj, vk);
+                x = grid_axis((int)vi, a.vs, a.origin);
+                y = grid_axis((int)vj, a.vs, a.origin);
+                z = grid_axis((int)vk, a.vs, a.origin);
             }
             const float xh = Elem<T>::round(x), yh = Elem<T>::round(y), zh = Elem<T>::round(z);
             u32x4 f;
@@ -723,15 +800,11 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
         }
         read_b(c, 32);
 
-        // ---- layer 0 (aux only), both parts through set A into LDS serially (set B still
-        // holds the previous tile's layer 7 part 1, folded into the output during L1p0); the
-        // previous tile's readers all passed the end barrier of its layer 7
-        run_part<T, FE_NONE, false>(c, accA, accB, 0, false, false, shp(1), 0, false);
-        acc_to_lds<T, false>(c, accA);
-        stamp(c);
-        run_part<T, FE_NONE, false>(c, accA, accB, 0, false, false, bias(2), 0, false);
-        acc_to_lds<T, true>(c, accA);
-        stamp(c);
+        // ---- layer 0 (aux only), both parts through VGPR temporaries into LDS serially (set B
+        // still holds the previous tile's layer 7 part 1, folded into the output during L1p0);
+        // the previous tile's readers all passed the end barrier of its layer 7
+        layer0_part<T, false>(c, shp(1));
+        layer0_part<T, true>(c, bias(2));
 
         // ---- two-part layers 1, 2 (and 3 when 512 wide).  L1p0 folds the previous tile's
         // layer 7 part 1 into its outputs (FE_FIN1); p1 of layer l publishes with its end barrier
@@ -752,7 +825,7 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
             // once every wave is done reading layer 3's inputs)
             run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, shp(2), 0, false);
             fs_bar();
-            acc_to_lds<T, true>(c, accA);
+            acc_to_lds<T>(c, accA);
             stamp(c);
             // layer 4 (K = 256, positions 16..31); part 0 -> early positions during part 1
             run_part<T, FE_NONE, false>(c, accA, accB, 16, false, false, shp(3), 16, true);
@@ -862,6 +935,7 @@ int decoder_fs_fwd(const ldm_decoder_t* w, const float* beta, const float* xyz, 
     a.k0 = k0;
     a.vs = vs;
     a.origin = origin;
+    a.gd = mode == kModeGrid ? grid_div(N) : GridDiv{0, 0, 0};
     const int grid = a.n_tiles < num_cus ? a.n_tiles : num_cus;
     // The brick instantiations are named after the grid / points ones, so the compiler emits
     // them last and the existing kernels keep their place in the code object: with the brick

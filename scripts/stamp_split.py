@@ -40,7 +40,7 @@ def part(name, kind):
             "E16": ("steps 0-15 + BAR", "E 16-31 + END"),
             "plain16": ("steps 0-15", "(none)"),
             "E0end16": ("E 0-15 + END", "(none)"),
-            "FIN1": ("E(prev L7p1) 0-15 + BAR + store", "steps 16-31"),
+            "FIN1": ("E(prev L7p1) 0-15 + BAR", "fin_store", "steps 16-31"),
             "FIN0": ("E 0-15", "steps 16-31 + END")}[kind]
     return [f"{name} aux"] + [f"{name} {x}" for x in segs]
 
