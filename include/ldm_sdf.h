@@ -690,6 +690,42 @@ int ldm_mesh_sdf(const float* verts, int V, const int32_t* faces, int F, const f
 int ldm_mesh_sdf_face_chunk(void);
 int64_t ldm_mesh_sdf_split_below(void);
 
+/* ---- nearest points and Chamfer distances (additive in ABI 7) ------------- */
+/* Clouds are fp32 [.][3].  Every point pair is evaluated, as dx = a.x - b.x (dy, dz alike),
+ * d = dx dx, d = fma(dy, dy, d), d = fma(dz, dz, d): squared distances, |d - exact| <= 5 u d.
+ * Coordinates must be finite: the minimum drops a NaN, so the kernels cannot be relied on to
+ * propagate one; excluding them is the caller's.
+ *
+ * ldm_nearest_points: for q [P][3] against c [Q][3],
+ *   d2   [P]  min_j |q_i - c_j|^2
+ *   idx  [P]  (or NULL) the j of that minimum, the smaller index on a tie
+ * ldm_chamfer_matrix: for a [S][n][3] against b [R][m][3],
+ *   out  [S][R]  D(a_s -> b_r) = (1 / n) sum_i min_j |a_si - b_rj|^2: the n minima (bitwise those
+ *                of ldm_nearest_points) added in fp64 in an order fixed by n and
+ *                ldm_chamfer_tile_a() alone, then fl32(sum / n)
+ * The other direction is the same call with the arguments swapped.  out[s][r] is a pure
+ * function of (a_s, b_r), bitwise: the same for any S and R, at any position, from run to run.
+ * P == 0, S == 0 or R == 0 return 0 with nothing written.  LDM_EINVAL for a NULL pointer, a
+ * negative count, Q == 0 / n == 0 / m == 0 with work to do, and a grid beyond the launch limits
+ * (Q, n or m above 2^31 - 1; S x R above 2^31 - 1; P above (2^31 - 1) ldm_chamfer_tile_a());
+ * LDM_EALIGN for tensors off 4 B or a workspace off 256 B; LDM_ENOSPC for a short workspace.
+ * ws: 256-byte aligned, ldm_nearest_points_ws_bytes(P, Q) / ldm_chamfer_ws_bytes(S, n, R, m)
+ * bytes (0 for arguments the call refuses); bounded by the tiling, never S x R x n. */
+size_t ldm_nearest_points_ws_bytes(int64_t P, int64_t Q);
+int ldm_nearest_points(const float* q, int64_t P, const float* c, int64_t Q, float* d2,
+                       int32_t* idx, void* ws, size_t ws_bytes, ldm_stream_t s);
+size_t ldm_chamfer_ws_bytes(int64_t S, int64_t n, int64_t R, int64_t m);
+int ldm_chamfer_matrix(const float* a, int64_t S, int64_t n, const float* b, int64_t R,
+                       int64_t m, float* out, void* ws, size_t ws_bytes, ldm_stream_t s);
+/* Host: points of the first cloud per workgroup tile; points of the second cloud per split
+ * unit; P below which ldm_nearest_points splits the second cloud over workgroups (with more than
+ * one unit of it); S x R below which ldm_chamfer_matrix spreads one entry over workgroups (with
+ * more than one tile of n). */
+int ldm_chamfer_tile_a(void);
+int ldm_chamfer_chunk_b(void);
+int64_t ldm_chamfer_split_below(void);
+int64_t ldm_chamfer_spread_below(void);
+
 #ifdef __cplusplus
 }
 #endif

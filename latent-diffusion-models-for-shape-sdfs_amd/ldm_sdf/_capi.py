@@ -235,6 +235,15 @@ SIGNATURES = [
     ("ldm_mesh_sdf", _i, [_fp, _i, _vp, _i, _fp, C.c_int64, _fp, _vp, _fp, _vp, _vp, _sz, _vp]),
     ("ldm_mesh_sdf_face_chunk", _i, []),
     ("ldm_mesh_sdf_split_below", C.c_int64, []),
+    ("ldm_nearest_points_ws_bytes", _sz, [C.c_int64, C.c_int64]),
+    ("ldm_nearest_points", _i, [_fp, C.c_int64, _fp, C.c_int64, _fp, _vp, _vp, _sz, _vp]),
+    ("ldm_chamfer_ws_bytes", _sz, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    ("ldm_chamfer_matrix", _i, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, C.c_int64, _fp, _vp,
+                                _sz, _vp]),
+    ("ldm_chamfer_tile_a", _i, []),
+    ("ldm_chamfer_chunk_b", _i, []),
+    ("ldm_chamfer_split_below", C.c_int64, []),
+    ("ldm_chamfer_spread_below", C.c_int64, []),
 ]
 
 _lib: Optional[C.CDLL] = None
