@@ -23,7 +23,8 @@
 //       - a layer's part 0 (set A) -> the "early" positions 0..15, during the SAME layer's
 //         part 1 steps 16-30: part 1 reads the early positions in steps 0-15, so after the
 //         barrier inside its step 15 no wave reads them any more; the barrier inside its
-//         step 31 publishes them to the next layer;
+//         step 31 publishes them to the next layer (layer 1 converts ahead instead, in its
+//         part 1's plain steps 8-15, and writes in steps 16-19: run_part);
 //       - layer 7's parts fold into the final 512 -> 1 dot product instead (fp32, w_last):
 //         part 0 during part 1, part 1 during the NEXT tile's layer 1 part 0 (which also
 //         stores the previous tile's outputs).
@@ -130,7 +131,14 @@ struct FArgs {
 //   FE_FIN1: layer 7 part 1 of the PREVIOUS tile (set B) -> the dot product, during layer 1 part
 //            0 of this one; its step 14 publishes the partials (the mid barrier) and the part
 //            sums them and stores the previous tile's outputs after that barrier
-enum FsEpi { FE_NONE = 0, FE_LATE = 1, FE_EARLY = 2, FE_FIN0 = 3, FE_FIN1 = 4 };
+//   FE_CVT / FE_WR: the two halves of an unpinned FE_EARLY in a 32-step part (run_part, the
+//            "ahead" form, layer 1 part 1 only): the set is converted into VGPR fragments during
+//            the plain steps 8-15 and written out in steps 16-19
+// FE_PIN (a flag on FE_LATE / FE_EARLY / FE_FIN0): read every element through acc_read() at its
+// use (FE_FIN1 always does).  Which sites carry it is decided per site from the assembly, see the
+// table at the call sites in dec_fs_kernel.
+enum FsEpi { FE_NONE = 0, FE_LATE = 1, FE_EARLY = 2, FE_FIN0 = 3, FE_FIN1 = 4, FE_CVT = 5,
+             FE_WR = 6, FE_PIN = 8 };
 
 // A fragment source: a buffer resource (SGPRs) + a byte offset (SGPR); the lane's 16 bytes at
 // voffset lane*16 (+1024: the second fragment, an immediate).  Raw buffer loads keep every
@@ -157,6 +165,7 @@ struct FCtx {
     u32x4 ring[kFsD][2];
     u32x4 b[4];               // the B fragments of the step about to run (rolling)
     float part[4];            // final-layer partial sums of point chunk n
+    u32x4 ef[16];             // FE_CVT -> FE_WR: the finished set as fragments, [tile 4i + n][s]
     float* out;               // the previous tile's outputs (FE_FIN1): [shape][npts]
     int npts, prev_shape, prev_local;   // prev_local < 0: no previous tile
     float b_last;
@@ -279,18 +288,23 @@ __device__ __forceinline__ float acc_read(float a) {
 
 // One epilogue unit u = 2t + s of the other accumulator set: HALF of tile t = 4i + n (its
 // accumulator registers 8s..8s+7 = the B fragment of k-step 2i + s).
-template <typename T, int EK>
-__device__ __forceinline__ void epi_unit(FCtx& c, const f32x16 (&accY)[2][4], int u) {
+// `wbase`: this wave's early / late positions (act_w), formed once per 4-step group.
+template <typename T, int EKP>
+__device__ __forceinline__ void epi_unit(FCtx& c, const f32x16 (&accY)[2][4], int u,
+                                         u32x4* wbase) {
+    constexpr int EK = EKP & 7;
+    constexpr bool PIN = (EKP & FE_PIN) != 0 || EK == FE_FIN1;
     const int t = u >> 1, s = u & 1;
     const int i = t >> 2, n = t & 3;
     if (FS_ABL & 2) return;
     if (EK == FE_LATE || EK == FE_EARLY) {   // part 1 of the previous layer / part 0 of this
         u32x4 f;
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            f[q] = relu2(Elem<T>::pack(accY[i][n][8 * s + 2 * q], accY[i][n][8 * s + 2 * q + 1]));
-        u32x4* p = act_w(c, EK == FE_LATE ? 16 : 0);
-        p[((2 * i + s) * 4 + n) * 64] = f;
+        for (int q = 0; q < 4; ++q) {
+            const float lo = accY[i][n][8 * s + 2 * q], hi = accY[i][n][8 * s + 2 * q + 1];
+            f[q] = relu2(PIN ? Elem<T>::pack(acc_read(lo), acc_read(hi)) : Elem<T>::pack(lo, hi));
+        }
+        wbase[((2 * i + s) * 4 + n) * 64] = f;
     } else if (EK == FE_FIN0 || EK == FE_FIN1) {     // layer 7 -> the final dot product
         const f32x4* w = wl_at(c, EK == FE_FIN0 ? 0 : 1, i);
         float part = c.part[n];
@@ -299,8 +313,7 @@ __device__ __forceinline__ void epi_unit(FCtx& c, const f32x16 (&accY)[2][4], in
             const f32x4 wv = w[q];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float v = EK == FE_FIN1 ? acc_read(accY[i][n][4 * q + e])
-                                              : accY[i][n][4 * q + e];
+                const float v = PIN ? acc_read(accY[i][n][4 * q + e]) : accY[i][n][4 * q + e];
                 part = fmaf(relu_f(v), wv[e], part);
             }
         }
@@ -311,11 +324,45 @@ __device__ __forceinline__ void epi_unit(FCtx& c, const f32x16 (&accY)[2][4], in
 // The 16 units of an epilogue window of 16 steps k = 0..15: unit k in step k < 14, units 14
 // and 15 in step 14, none in step 15 -- so the window's LDS writes are all issued before the
 // barrier that closes it (inside step 15, see group4).
-template <typename T, int EK>
-__device__ __forceinline__ void epi_step(FCtx& c, const f32x16 (&accY)[2][4], int k) {
+//
+// The ahead form of FE_EARLY (k = 0..7 / 0..3 here): FE_CVT step k converts tile k = 4i + n
+// (16 reads, 8 conversions, 8 ReLUs) into c.ef, FE_WR step k writes tiles 2k and 2k + 1.
+template <typename T, int EKP>
+__device__ __forceinline__ void epi_step(FCtx& c, const f32x16 (&accY)[2][4], int k,
+                                         u32x4* wbase) {
+    constexpr int EK = EKP & 7;
     if (EK == FE_NONE || k == 15) return;
-    epi_unit<T, EK>(c, accY, k);
-    if (k == 14) epi_unit<T, EK>(c, accY, 15);
+    if (EK == FE_CVT) {
+        if ((FS_ABL & 2) || k >= 8) return;
+        u32x4 f0, f1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x16& a = accY[k >> 2][k & 3];
+            f0[q] = relu2(Elem<T>::pack(acc_read(a[2 * q]), acc_read(a[2 * q + 1])));
+            f1[q] = relu2(Elem<T>::pack(acc_read(a[8 + 2 * q]), acc_read(a[8 + 2 * q + 1])));
+        }
+        c.ef[2 * k] = f0;
+        c.ef[2 * k + 1] = f1;
+        return;
+    }
+    if (EK == FE_WR) {
+        if ((FS_ABL & 2) || k >= 4) return;
+#pragma unroll
+        for (int t = 2 * k; t < 2 * k + 2; ++t) {
+            const int i = t >> 2, n = t & 3;
+            wbase[(2 * i * 4 + n) * 64] = c.ef[2 * t];
+            wbase[((2 * i + 1) * 4 + n) * 64] = c.ef[2 * t + 1];
+        }
+        return;
+    }
+    epi_unit<T, EKP>(c, accY, k, wbase);
+    if (k == 14) epi_unit<T, EKP>(c, accY, 15, wbase);
+    if (EK == FE_FIN0 && k == 14) {
+        // the partial sums are next used in the next tile: fix them HERE, or the whole chain of
+        // FMAs is sunk below the part's plain steps and its 128 inputs are kept (and spilled)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) asm volatile("" : "+v"(c.part[n]));
+    }
     if (EK == FE_FIN1 && k == 14) {         // the partials -> red[wave][n][lane], published by
         float* rw = red_w(c);               // the barrier inside step 15
 #pragma unroll
@@ -431,10 +478,16 @@ __device__ __forceinline__ void mfma_pair(f32x16 (&acc)[2][4], const u32x4& a0, 
 // the waves wait on each other with the step's remaining MFMAs still to issue and the next
 // position's reads still covered by them (a barrier between steps exposed one LDS round trip
 // plus the pipeline drain, ~500-750 cycles per barrier).
-template <typename T, int EK, int K0, int BAR>
+template <typename T, int EKP, int K0, int BAR>
 __device__ __forceinline__ void group4(FCtx& c, f32x16 (&acc)[2][4], const f32x16 (&accY)[2][4],
                                        int p0) {
+    constexpr int EK = EKP & 7;
     constexpr int BP = 1;                    // MFMA pairs before the in-stream barrier
+    // likewise ONE base for the group's epilogue writes (the unit's position is an immediate);
+    // formed per unit it cost v_mov + s_nop + v_add in steps that are issue-bound
+    u32x4* wbase = nullptr;
+    if (EK == FE_LATE) wbase = act_w(c, 16);
+    if (EK == FE_EARLY || EK == FE_WR) wbase = act_w(c, 0);
     // ONE LDS base for the group's four next positions (r * 4 KiB + n * 1 KiB fold into the
     // ds_read immediates) instead of an address formed per step
     const char* gbase = lds_at(c, (p0 + 1) * 4096);
@@ -445,7 +498,9 @@ __device__ __forceinline__ void group4(FCtx& c, f32x16 (&acc)[2][4], const f32x1
         const int k = K0 + r;
         // the step's VALU (epilogue: AGPR reads, cvt, ReLU, LDS address) 2 per MFMA gap, 4 in
         // the double-unit step 14 (the guide: <= 5 fillers per 32x32x16 gap hide)
-        const int V = (EK == FE_NONE || k == 15) ? 0 : (k == 14 ? 4 : 2);
+        // (FE_CVT: 32 VALU a step, in steps that carry nothing else)
+        const int V = (EK == FE_NONE || EK == FE_WR || k == 15) ? 0
+                      : (k == 14 || EK == FE_CVT) ? 4 : 2;
         if (r == BAR) {
 #pragma unroll
             for (int n = 0; n < BP; ++n) mfma_pair<T>(acc, a0, a1, c.b[n], n);
@@ -463,7 +518,7 @@ __device__ __forceinline__ void group4(FCtx& c, f32x16 (&acc)[2][4], const f32x1
                 c.b[n] = nb[n * 64];
             }
             issue(c, r);
-            epi_step<T, EK>(c, accY, k);
+            epi_step<T, EKP>(c, accY, k, wbase);
             for (int n = 0; n < BP; ++n) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             for (int n = BP; n < 4; ++n) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -479,7 +534,7 @@ __device__ __forceinline__ void group4(FCtx& c, f32x16 (&acc)[2][4], const f32x1
                 c.b[n] = nb[n * 64];
             }
             issue(c, r);
-            epi_step<T, EK>(c, accY, k);
+            epi_step<T, EKP>(c, accY, k, wbase);
             // pin the step's order for the scheduler (left free it sank the B reads and weight
             // loads below the last MFMA): per point chunk n, MFMA, [VALU], MFMA, B read,
             // [VALU]; then the 2 weight loads
@@ -524,15 +579,20 @@ __device__ __forceinline__ void steps_plain(FCtx& c, f32x16 (&acc)[2][4],
 //     and, per point chunk, reads the first position's B fragment behind its MFMA pair -- or,
 //     `bar0`, after a barrier (the part follows serial LDS writes: layers 1 and 4 at skip 253);
 //     then it loads the NEXT part's aux A fragments (naux).
-//   * E work (the other set, EK) in steps 0-15 (E16 false) or 16-31 (E16 true).
+//   * E work (the other set, EK) in steps 0-15 (E16 false) or, E16 (FE_EARLY of a 32-step
+//     part), in steps 16-31 with FE_PIN.  E16 without FE_PIN is the ahead form: converted in
+//     the plain steps 8-15 (FE_CVT) and written in steps 16-19 (FE_WR), steps 20-27 a rolled
+//     loop again.  Only layer 1 part 1 uses it: pinned in its window it cost the bf16 skip-253
+//     instances 160 v_accvgpr_mov / _write.
 //   * `mid`: the barrier inside step 15 (the late positions written during steps 0-14 by
 //     every wave / no wave reads the early positions any more before E16 writes them);
 //     `endbar` (E work parts): the barrier inside the part's last step, publishing the window's
 //     writes to the next part, whose aux step then reads on without a barrier.
-template <typename T, int EK, bool E16, int MODE = kModeGrid>
+template <typename T, int EKP, bool E16, int MODE = kModeGrid>
 __device__ __forceinline__ void run_part(FCtx& c, f32x16 (&acc)[2][4], const f32x16 (&accY)[2][4],
                                          int nk, bool mid, bool endbar, FSrc naux, int pos0,
                                          bool bar0) {
+    constexpr int EK = EKP & 7;
     const f32x16 zero = {};
     const u32x4 a0 = c.auxn[0], a1 = c.auxn[1];
     if (bar0) {
@@ -561,11 +621,24 @@ __device__ __forceinline__ void run_part(FCtx& c, f32x16 (&acc)[2][4], const f32
         __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
+    if (EK == FE_NONE) {
+        // A part without E work (layer 4 part 0 at skip 253) starts with BOTH sets dead: the
+        // other one was converted during the previous part, this one written out serially.
+        // Everywhere else the other set is live across the aux step, so the new accumulators
+        // can only take the registers of the set they replace; here they could take either
+        // half of the file, and when they took the other set's the two sets had traded places
+        // by the end of the tile and were moved back (v_accvgpr_mov, spills).  An empty asm
+        // statement that names the dead set keeps its registers occupied across this aux step.
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) asm volatile("" ::"a"(accY[i][n]));
+    }
     stamp(c);
     if (!E16 && EK != FE_NONE) {        // E work in steps 0-15
         // the barrier inside step 15: mid (nk 32), or the end barrier of a 16-step part
-        if (mid || (endbar && nk == 16)) steps16e<T, EK, true>(c, acc, accY, pos0);
-        else steps16e<T, EK, false>(c, acc, accY, pos0);
+        if (mid || (endbar && nk == 16)) steps16e<T, EKP, true>(c, acc, accY, pos0);
+        else steps16e<T, EKP, false>(c, acc, accY, pos0);
         if (EK == FE_FIN1) {
             stamp(c);
             fin_store_mode<MODE>(c);
@@ -577,12 +650,21 @@ __device__ __forceinline__ void run_part(FCtx& c, f32x16 (&acc)[2][4], const f32
         } else {
             steps_plain<T>(c, acc, accY, pos0, 16, nk);
         }
-    } else if (E16) {                   // nk 32, mid
+    } else if (E16 && (EKP & FE_PIN)) {     // nk 32, mid: the window in steps 16-31
         steps_plain<T>(c, acc, accY, pos0, 0, 12);
         group4<T, FE_NONE, 0, 3>(c, acc, accY, pos0 + 12);
         stamp(c);
-        if (endbar) steps16e<T, EK, true>(c, acc, accY, pos0 + 16);
-        else steps16e<T, EK, false>(c, acc, accY, pos0 + 16);
+        if (endbar) steps16e<T, EKP, true>(c, acc, accY, pos0 + 16);
+        else steps16e<T, EKP, false>(c, acc, accY, pos0 + 16);
+    } else if (E16) {                   // nk 32, mid, endbar, FE_EARLY unpinned: the ahead form
+        static_assert(!E16 || EK == FE_EARLY, "E16 parts convert part 0 of their own layer");
+        steps_plain<T>(c, acc, accY, pos0, 0, 8);
+        group4<T, FE_CVT, 0, -1>(c, acc, accY, pos0 + 8);
+        group4<T, FE_CVT, 4, 3>(c, acc, accY, pos0 + 12);
+        stamp(c);
+        group4<T, FE_WR, 0, -1>(c, acc, accY, pos0 + 16);
+        steps_plain<T>(c, acc, accY, pos0, 20, 28);
+        group4<T, FE_NONE, 0, 3>(c, acc, accY, pos0 + 28);
     } else {                            // plain part, no barrier (layer 4 part 0 at skip 253)
         steps_plain<T>(c, acc, accY, pos0, 0, nk < 16 ? nk : 16);
         stamp(c);
@@ -807,7 +889,17 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
         layer0_part<T, true>(c, bias(2));
 
         // ---- two-part layers 1, 2 (and 3 when 512 wide).  L1p0 folds the previous tile's
-        // layer 7 part 1 into its outputs (FE_FIN1); p1 of layer l publishes with its end barrier
+        // layer 7 part 1 into its outputs (FE_FIN1); p1 of layer l publishes with its end barrier.
+        // FE_PIN per site, from the assembly of all 12 instances (tests/
+        // test_decoder_window_codegen.py).  Without it the allocator copies the finished set
+        // into VGPRs in one burst at the part's start, with the matrix pipe idle; with it on a
+        // site that needs none it shuffles accumulators (v_accvgpr_mov / _write) instead.  The
+        // windows of layers 5, 6 and 7 part 0, of layer 7 part 1 (FE_FIN0), of layer 4 part 1
+        // at skip 253 and of every part 1 from layer 2 on carry it (layer 1 part 1 converts
+        // ahead, see run_part); those of layer 2 (and 3) part 0 and the last one before layer
+        // 4 only in the regular 512-wide layer order (at skip 253, where layer 3 is one part,
+        // they read in place as they are and the pin costs 368 moves).
+        constexpr int kPinW = S == 512 ? FE_PIN : 0;
         int pi = 2;
         run_part<T, FE_FIN1, false, MODE>(c, accA, accB, 32, true, false, bias(pi + 1), 0, true);
         run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0, false);
@@ -817,39 +909,46 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
         for (int l = 2; l < L2P; ++l, pi += 2) {
             // the part after layer 3 (512 wide) is layer 4's: per-shape aux
             const FSrc nx = (S == 512 && l == 3) ? shp(2) : bias(pi + 2);
-            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0, false);
-            run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, nx, 0, false);
+            run_part<T, FE_LATE | kPinW, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0,
+                                                false);
+            run_part<T, FE_EARLY | FE_PIN, true>(c, accB, accA, 32, true, true, nx, 0, false);
         }
         if (S == 256) {
             // layer 3: one part of rows 64w..64w+63 -> positions 16 + 4w + 2i + s (serial,
             // once every wave is done reading layer 3's inputs)
-            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, shp(2), 0, false);
+            run_part<T, FE_LATE | kPinW, false>(c, accA, accB, 32, true, false, shp(2), 0,
+                                                false);
             fs_bar();
             acc_to_lds<T>(c, accA);
             stamp(c);
             // layer 4 (K = 256, positions 16..31); part 0 -> early positions during part 1
             run_part<T, FE_NONE, false>(c, accA, accB, 16, false, false, shp(3), 16, true);
-            run_part<T, FE_EARLY, false>(c, accB, accA, 16, false, true, bias(pi + 3), 16,
-                                             false);
+            run_part<T, FE_EARLY | FE_PIN, false>(c, accB, accA, 16, false, true, bias(pi + 3),
+                                                  16, false);
             pi += 3;
         } else {
-            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, shp(3), 0, false);
-            run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0, false);
+            run_part<T, FE_LATE | kPinW, false>(c, accA, accB, 32, true, false, shp(3), 0,
+                                                false);
+            run_part<T, FE_EARLY | FE_PIN, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0,
+                                                 false);
             pi += 2;
         }
         // ---- layers 5, 6
 #pragma unroll 1
         for (int l = 5; l < 7; ++l, pi += 2) {
-            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0, false);
-            run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0, false);
+            run_part<T, FE_LATE | FE_PIN, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0,
+                                                 false);
+            run_part<T, FE_EARLY | FE_PIN, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0,
+                                                 false);
         }
         // ---- layer 7: part 0 folds into the dot product during part 1, part 1 during the
         // next tile's L1p0 (its end barrier lets the next tile overwrite every position)
-        run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0, false);
+        run_part<T, FE_LATE | FE_PIN, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0,
+                                             false);
         // (no prefetch of the next tile's first aux fragments here: live across the whole
         // part they were spilled, each spill waiting for the whole ring)
-        run_part<T, FE_FIN0, false>(c, accB, accA, 32, false, true, FSrc{true, 0, true}, 0,
-                                        false);
+        run_part<T, FE_FIN0 | FE_PIN, false>(c, accB, accA, 32, false, true, FSrc{true, 0, true},
+                                             0, false);
         c.prev_shape = shape;
         c.prev_local = local;
         c.aux_w = c.aux_next;
@@ -857,7 +956,7 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
     // the last tile's layer 7 part 1: the FE_FIN1 units in their window order (a point's
     // value must not depend on whether its tile was its workgroup's last)
 #pragma unroll
-    for (int u = 0; u < 16; ++u) epi_unit<T, FE_FIN1>(c, accB, u);
+    for (int u = 0; u < 16; ++u) epi_unit<T, FE_FIN1>(c, accB, u, nullptr);
     {
         float* rw = red_w(c);
 #pragma unroll
