@@ -726,6 +726,53 @@ int ldm_chamfer_chunk_b(void);
 int64_t ldm_chamfer_split_below(void);
 int64_t ldm_chamfer_spread_below(void);
 
+/* ---- earth mover's distance (additive in ABI 7) ---------------------------- */
+/* For clouds of the same size n (fp32 [.][n][3], finite coordinates: the caller's to ensure),
+ *   EMD(a, b) = (1 / n) min over permutations pi of sum_i |a_i - b_pi(i)|        (Euclidean).
+ * The pair distance is the squared distance of the Chamfer calls (same operation sequence)
+ * followed by one square root of at most 1 ulp (v_sqrt_f32): |d - exact| <= 5 u |exact|,
+ * u = 2^-24 (the 5 u of d^2 halve under the root, which adds up to 2 u of its own).
+ *
+ * ldm_emd_matrix runs an eps-scaled Jacobi auction per entry, one workgroup each, and returns a
+ * real assignment.  With cost = (1 / n) sum_i |a_i - b_pi(i)| in exact arithmetic,
+ *   EMD <= cost <= EMD + eps + ldm_emd_slack(extent)
+ * (eps-complementary slackness; the slack is what fp32 rounding of values and bids adds, see
+ * below).  out [S][R] = fl32(sum of the n fp32 pair distances, added in fp64 in an order fixed by
+ * n alone, / n): within 6 u of cost.  An entry is a pure function of (a_s, b_r, eps), bitwise:
+ * the same for any S and R, at any position, from run to run.
+ *   eps          > 0: the bound above, in the units of the coordinates
+ *   extent       an upper bound of the bounding-box diagonal of every pair (a_s with b_r) the
+ *                caller vouches for; an entry whose own diagonal is larger is not computed
+ *   max_rounds   most auction rounds per entry; 0: ldm_emd_default_max_rounds(n)
+ *   within       nonzero: b == a and R == S; only s < r is computed, mirrored into r > s (the
+ *                assignment inverted), and the diagonal is an exact 0 with the identity
+ *   assign       [S][R][n] int32 or NULL: pi, the index into b_r that point i of a_s is matched to
+ *   rounds       [S][R] int32 or NULL: auction rounds the entry took
+ *   unconverged  one int32 or NULL: set to the number of entries not computed: round cap hit,
+ *                extent above the bound, or a bid outside (price, 8 extent + 4 eps].  Such an
+ *                entry is NaN in out and -1 throughout assign; the launch still ends.
+ * The slack: values d + price and bids are rounded to fp32, which loosens eps-complementary
+ * slackness by at most 5 u (extent + largest price) per pair; the kernel holds prices to
+ * 8 extent + 4 eps, and the fp32 distances move both costs by at most 5 u extent each:
+ * ldm_emd_slack(extent) = 55 u extent.  ldm_emd_min_eps(extent) = 8 ldm_emd_slack(extent) is the
+ * smallest eps the call accepts, so that the slack stays under eps / 8.
+ * S == 0 or R == 0 return 0 with nothing written.  LDM_EINVAL for a NULL a / b / out / ws, a
+ * negative count, n == 0 with work to do, S x R above 2^31 - 1, within without b == a and
+ * R == S, an extent that is negative or not finite, eps not positive, not finite or below the
+ * floor, max_rounds outside [0, 2^31 - 1]; LDM_ENOSYS for n above ldm_emd_max_points();
+ * LDM_EALIGN for tensors off 4 B or a workspace off 256 B; LDM_ENOSPC for a short workspace.
+ * Every refusal happens before any device work.  ws: 256-byte aligned, ldm_emd_ws_bytes(S, R, n)
+ * bytes (0 for negative or oversized counts); it holds the count when unconverged is NULL. */
+size_t ldm_emd_ws_bytes(int64_t S, int64_t R, int64_t n);
+int ldm_emd_matrix(const float* a, int64_t S, const float* b, int64_t R, int64_t n, float eps,
+                   float extent, int64_t max_rounds, int within, float* out, int32_t* assign,
+                   int32_t* rounds, int32_t* unconverged, void* ws, size_t ws_bytes,
+                   ldm_stream_t s);
+int64_t ldm_emd_max_points(void);
+double ldm_emd_slack(double extent);
+double ldm_emd_min_eps(double extent);
+int64_t ldm_emd_default_max_rounds(int64_t n); /* 0 for n outside [1, ldm_emd_max_points()] */
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,8 +17,9 @@ from .autodecoder import (AutoDecoderState, autodecoder_train_step,  # noqa: F40
                           train_autodecoder)
 from .grad import fit_latents, sdf_grad  # noqa: F401
 from .meshsdf import mesh_sdf, normalize_mesh, sample_sdf, sample_surface  # noqa: F401
-from .metrics import (chamfer_distance, chamfer_matrix, evaluate_generation,  # noqa: F401
-                      generation_metrics, nearest_points, shape_clouds)
+from .metrics import (chamfer_distance, chamfer_matrix, emd_distance,  # noqa: F401
+                      emd_matrix, evaluate_generation, generation_metrics, nearest_points,
+                      shape_clouds)
 from . import ops, dist, pack, data, meshsdf, metrics  # noqa: F401
 from ._capi import LdmError, load as load_library  # noqa: F401
 

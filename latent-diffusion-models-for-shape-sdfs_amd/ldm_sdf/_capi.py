@@ -244,6 +244,13 @@ SIGNATURES = [
     ("ldm_chamfer_chunk_b", _i, []),
     ("ldm_chamfer_split_below", C.c_int64, []),
     ("ldm_chamfer_spread_below", C.c_int64, []),
+    ("ldm_emd_ws_bytes", _sz, [C.c_int64, C.c_int64, C.c_int64]),
+    ("ldm_emd_matrix", _i, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, _f, _f, C.c_int64, _i,
+                            _fp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    ("ldm_emd_max_points", C.c_int64, []),
+    ("ldm_emd_slack", C.c_double, [C.c_double]),
+    ("ldm_emd_min_eps", C.c_double, [C.c_double]),
+    ("ldm_emd_default_max_rounds", C.c_int64, [C.c_int64]),
 ]
 
 _lib: Optional[C.CDLL] = None

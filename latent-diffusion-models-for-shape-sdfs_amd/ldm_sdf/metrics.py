@@ -7,6 +7,10 @@ Chamfer matrices into MMD, COV and 1-NNA (Achlioptas et al.; Yang et al., PointF
 torch on any device.  ``shape_clouds`` draws the clouds from latents through ``extract_mesh`` and
 ``sample_surface``.
 
+``emd_matrix`` and ``emd_distance`` run the auction kernel of ``csrc/emd.hip``:
+the earth mover's distance ``(1/n) min_pi sum_i |a_i - b_pi(i)|`` of clouds of equal size, from a
+real assignment whose cost is within ``eps + emd_slack(extent)`` of the optimum.
+
 An entry of a matrix is a pure function of its two clouds: bitwise the same alone or in any
 batch, at any position, from run to run.
 """
@@ -20,7 +24,8 @@ from . import _capi as capi
 
 __all__ = ["nearest_points", "chamfer_matrix", "chamfer_distance", "generation_metrics",
            "evaluate_generation", "shape_clouds", "tile_a", "chunk_b", "split_below",
-           "spread_below"]
+           "spread_below", "emd_matrix", "emd_distance", "emd_max_points", "emd_min_eps",
+           "emd_slack", "emd_default_max_rounds"]
 
 
 def tile_a() -> int:
@@ -186,16 +191,145 @@ def generation_metrics(cd_gr: torch.Tensor, cd_gg: torch.Tensor, cd_rr: torch.Te
     return {"mmd": mmd, "cov": cov, "1nna": nna}
 
 
+def emd_max_points() -> int:
+    """Most points per cloud ``emd_matrix`` takes (one workgroup keeps a pair in LDS)."""
+    return int(capi.load().ldm_emd_max_points())
+
+
+def emd_slack(extent: float) -> float:
+    """What fp32 rounding adds to ``eps`` in the bound ``cost <= EMD + eps + slack`` for clouds
+    whose common bounding box has the diagonal ``extent``."""
+    return float(capi.load().ldm_emd_slack(float(extent)))
+
+
+def emd_min_eps(extent: float) -> float:
+    """The smallest ``eps`` accepted at that extent: ``8 emd_slack(extent)``."""
+    return float(capi.load().ldm_emd_min_eps(float(extent)))
+
+
+def emd_default_max_rounds(n: int) -> int:
+    """The default cap on auction rounds per entry for clouds of ``n`` points."""
+    return int(capi.load().ldm_emd_default_max_rounds(int(n)))
+
+
+def _extent_bound(a: torch.Tensor, b: Optional[torch.Tensor]) -> float:
+    """fp32 upper bound of the bounding-box diagonal of all the clouds together."""
+    lo, hi = a.amin(dim=(0, 1)), a.amax(dim=(0, 1))
+    if b is not None:
+        lo, hi = torch.minimum(lo, b.amin(dim=(0, 1))), torch.maximum(hi, b.amax(dim=(0, 1)))
+    diag = float(torch.linalg.vector_norm((hi - lo).double()))
+    return float(torch.tensor(diag * (1 + 2.0 ** -20), dtype=torch.float64).float()
+                 .nextafter(torch.tensor(float("inf"))))
+
+
+def _emd(a: torch.Tensor, b: Optional[torch.Tensor], eps: float, max_rounds: Optional[int],
+         want_assign: bool, what: str, validated: bool = False):
+    """``(out [S, R], assign or None, rounds [S, R])``; raises for unconverged entries."""
+    _check_cloud(a, 3, f"{what}: a")
+    if b is not None:
+        _check_cloud(b, 3, f"{what}: b")
+    capi.require_device(a, b)
+    other = a if b is None else b
+    if a.device != other.device:
+        raise capi.LdmError(f"{what}: a and b must share a device")
+    S, R, n = a.shape[0], other.shape[0], a.shape[1]
+    if other.shape[1] != n:
+        raise capi.LdmError(f"{what}: clouds of {n} and {other.shape[1]} points: the earth "
+                            "mover's distance here is between clouds of the same size")
+    if max_rounds is not None and int(max_rounds) < 1:
+        raise capi.LdmError(f"{what}: max_rounds must be at least 1 (None: the default)")
+    dev = a.device
+    out = torch.empty(S, R, device=dev, dtype=torch.float32)
+    rounds = torch.zeros(S, R, device=dev, dtype=torch.int32)
+    assign = torch.empty(S, R, n, device=dev, dtype=torch.int32) if want_assign else None
+    if S == 0 or R == 0:
+        return out, assign, rounds
+    if n == 0:
+        raise capi.LdmError(f"{what}: empty clouds have no distance")
+    lib = capi.load()
+    if n > lib.ldm_emd_max_points():
+        raise capi.LdmError(f"{what}: {n} points per cloud is above emd_max_points() = "
+                            f"{lib.ldm_emd_max_points()}")
+    if not validated:
+        _check_finite(a, f"{what}: a")
+        if b is not None:
+            _check_finite(b, f"{what}: b")
+    extent = _extent_bound(a, b)
+    if not (eps > 0 and eps >= lib.ldm_emd_min_eps(extent)):
+        raise capi.LdmError(f"{what}: eps = {eps:g} is below emd_min_eps({extent:g}) = "
+                            f"{lib.ldm_emd_min_eps(extent):g}, the floor under which fp32 "
+                            "rounding is no longer small against eps")
+    a = a.contiguous()
+    bb = a if b is None else b.contiguous()
+    unconv = torch.zeros(1, device=dev, dtype=torch.int32)
+    ws = torch.empty(lib.ldm_emd_ws_bytes(S, R, n), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        capi.check(lib.ldm_emd_matrix(capi.ptr(a), S, capi.ptr(bb), R, n, float(eps), extent,
+                                      0 if max_rounds is None else int(max_rounds),
+                                      1 if b is None else 0, capi.ptr(out), capi.ptr(assign),
+                                      capi.ptr(rounds), capi.ptr(unconv), capi.ptr(ws),
+                                      ws.numel(), capi.stream_handle(dev)), "ldm_emd_matrix")
+    if int(unconv.item()):
+        bad = torch.nonzero(torch.isnan(out)).tolist()
+        cap = emd_default_max_rounds(n) if max_rounds is None else int(max_rounds)
+        raise capi.LdmError(f"{what}: {len(bad)} entries did not converge within {cap} rounds "
+                            f"(or left the price range): {[tuple(e) for e in bad[:16]]}"
+                            + (" ..." if len(bad) > 16 else ""))
+    return out, assign, rounds
+
+
+def emd_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None, *, eps: float = 1e-4,
+               max_rounds: Optional[int] = None, return_rounds: bool = False,
+               _validated: bool = False):
+    """Earth mover's distances ``[S, R]`` between the clouds ``a [S, n, 3]`` and ``b [R, n, 3]``
+    (fp32, device tensors, the same ``n``): each entry is the cost of a real assignment, at most
+    ``eps + emd_slack(extent)`` above the optimum.  ``b=None`` is the within-set matrix
+    (symmetric, zero diagonal; only ``s < r`` is computed).  ``max_rounds`` caps the auction
+    rounds per entry (default ``emd_default_max_rounds(n)``); an entry that hits it raises
+    ``LdmError`` naming it.  With ``return_rounds`` also the rounds per entry ``[S, R]`` int32.
+    A non-finite coordinate, ``n`` above ``emd_max_points()`` or an ``eps`` below
+    ``emd_min_eps(extent)`` raises ``LdmError``."""
+    out, _, rounds = _emd(a, b, eps, max_rounds, False, "emd_matrix", _validated)
+    return (out, rounds) if return_rounds else out
+
+
+def emd_distance(a: torch.Tensor, b: torch.Tensor, *, eps: float = 1e-4,
+                 return_assignment: bool = False):
+    """``EMD(a, b)`` of two clouds ``[n, 3]`` as a 0-d tensor; with ``return_assignment`` also
+    ``pi [n]`` int32, the point of ``b`` each point of ``a`` is matched to.  One workgroup does
+    the pair."""
+    _check_cloud(a, 2, "emd_distance: a")
+    _check_cloud(b, 2, "emd_distance: b")
+    capi.require_device(a, b)
+    out, assign, _ = _emd(a[None], b[None], eps, None, return_assignment, "emd_distance")
+    return (out[0, 0], assign[0, 0]) if return_assignment else out[0, 0]
+
+
 def evaluate_generation(gen_clouds: torch.Tensor, ref_clouds: torch.Tensor, *,
+                        metrics=("cd",), eps: float = 1e-4,
                         _validated: bool = False) -> Dict[str, object]:
     """MMD-CD, COV-CD and 1-NNA-CD of ``gen_clouds [S, n, 3]`` against ``ref_clouds [R, m, 3]``:
     four directed passes (G -> R, R -> G, G -> G, R -> R), then ``generation_metrics``.  The
-    result also carries the three matrices under ``cd_gr``, ``cd_gg`` and ``cd_rr``."""
+    result also carries the three matrices under ``cd_gr``, ``cd_gg`` and ``cd_rr``.
+
+    With ``"emd"`` in ``metrics`` (which needs ``n == m``) the result also has ``mmd_emd``,
+    ``cov_emd`` and ``1nna_emd``, ``generation_metrics`` of the earth mover's matrices, and those
+    matrices under ``emd_gr``, ``emd_gg`` and ``emd_rr``; ``eps`` is ``emd_matrix``'s."""
+    metrics = tuple(metrics)
+    if "cd" not in metrics or any(m not in ("cd", "emd") for m in metrics):
+        raise capi.LdmError("evaluate_generation: metrics must be ('cd',) or ('cd', 'emd')")
     cd_gr = chamfer_matrix(gen_clouds, ref_clouds, _validated=_validated)
     cd_gg = chamfer_matrix(gen_clouds, _validated=True)
     cd_rr = chamfer_matrix(ref_clouds, _validated=True)
     out: Dict[str, object] = dict(generation_metrics(cd_gr, cd_gg, cd_rr))
     out.update(cd_gr=cd_gr, cd_gg=cd_gg, cd_rr=cd_rr)
+    if "emd" in metrics:
+        emd_gr = emd_matrix(gen_clouds, ref_clouds, eps=eps, _validated=True)
+        emd_gg = emd_matrix(gen_clouds, eps=eps, _validated=True)
+        emd_rr = emd_matrix(ref_clouds, eps=eps, _validated=True)
+        out.update({k + "_emd": v
+                    for k, v in generation_metrics(emd_gr, emd_gg, emd_rr).items()})
+        out.update(emd_gr=emd_gr, emd_gg=emd_gg, emd_rr=emd_rr)
     return out
 
 
