@@ -773,6 +773,40 @@ double ldm_emd_slack(double extent);
 double ldm_emd_min_eps(double extent);
 int64_t ldm_emd_default_max_rounds(int64_t n); /* 0 for n outside [1, ldm_emd_max_points()] */
 
+/* ---- ray casting against a mesh (additive in ABI 7) ------------------------ */
+/* For R rays origins [R][3], dirs [R][3] (fp32; a direction need not be unit) against the
+ * triangle soup verts fp32 [V][3], faces int32 [F][3], every ray-triangle pair evaluated with
+ * the watertight test of Woop, Benthin and Wald in plain fp32 (csrc/ray_tri_pair.h: no fused
+ * multiply-add, true divisions; a ray through a shared edge or vertex of a closed mesh hits
+ * one of the triangles around it):
+ *   t_out    [R]     the smallest t in [t_min, t_max] with origin + t dir on a triangle (both
+ *                    sides of a triangle count); +inf for a miss
+ *   face_out [R]     (or NULL) index of that triangle, the smaller index on a tie; -1 for a miss
+ *   bary_out [R][3]  (or NULL) the weights of the triangle's three vertices at the hit, 0 for a
+ *                    miss
+ * A ray whose dominant direction component is 0 or not finite, or whose origin is not finite,
+ * misses everything.  A ray's outputs are a pure function of the ray, the mesh and the bounds:
+ * bitwise the same alone or in any batch, and from run to run.  F == 0 gives all misses;
+ * R == 0 returns 0 with nothing written.
+ * A face index outside [0, V) is never read through: it is clamped, and the device word *flag
+ * (zeroed by the call) is set to 1 -- the outputs are then meaningless.
+ * ws: 256-byte aligned, ldm_ray_mesh_ws_bytes(F, R) bytes (0 for negative sizes); it holds the
+ * packed triangles and, below ldm_ray_mesh_split_below() rays with more than one chunk of
+ * ldm_ray_mesh_face_chunk() faces, one tile of per-chunk partials.
+ * LDM_EINVAL for a NULL verts / faces (with F > 0) / origins / dirs / t_out / flag / ws, a
+ * negative count, t_min > t_max or a NaN bound, and a grid beyond the launch limits: more than
+ * 65535 chunks of faces in the split form, more than 2^31 - 1 workgroups of 256 rays in the
+ * other.  LDM_EALIGN for tensors off 4 B or a workspace off 256 B; LDM_ENOSPC for a short
+ * workspace.  Every refusal happens before any device work. */
+size_t ldm_ray_mesh_ws_bytes(int F, int64_t R);
+int ldm_ray_mesh(const float* verts, int V, const int32_t* faces, int F, const float* origins,
+                 const float* dirs, int64_t R, float t_min, float t_max, float* t_out,
+                 int32_t* face_out, float* bary_out, int32_t* flag, void* ws, size_t ws_bytes,
+                 ldm_stream_t s);
+/* Host: faces per workgroup of the split form, and the R below which it is used. */
+int ldm_ray_mesh_face_chunk(void);
+int64_t ldm_ray_mesh_split_below(void);
+
 #ifdef __cplusplus
 }
 #endif

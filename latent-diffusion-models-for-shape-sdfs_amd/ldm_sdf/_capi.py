@@ -251,6 +251,11 @@ SIGNATURES = [
     ("ldm_emd_slack", C.c_double, [C.c_double]),
     ("ldm_emd_min_eps", C.c_double, [C.c_double]),
     ("ldm_emd_default_max_rounds", C.c_int64, [C.c_int64]),
+    ("ldm_ray_mesh_ws_bytes", _sz, [_i, C.c_int64]),
+    ("ldm_ray_mesh", _i, [_fp, _i, _vp, _i, _fp, _fp, C.c_int64, _f, _f, _fp, _vp, _fp, _vp, _vp,
+                          _sz, _vp]),
+    ("ldm_ray_mesh_face_chunk", _i, []),
+    ("ldm_ray_mesh_split_below", C.c_int64, []),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -1123,3 +1123,31 @@ def denoiser_backward_train(model, dev: Dict[str, object], sv: dict,
     gt = silu_bwd(du, sv["a_t"])
     linear(gt.T, sv["e"].T, grads["Wt1"], compute=cp)
     colsum(gt, grads["bt1"])
+
+
+def ray_mesh(verts: torch.Tensor, faces: torch.Tensor, origins: torch.Tensor,
+             dirs: torch.Tensor, t_min: float, t_max: float, want_bary: bool
+             ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """ldm_ray_mesh on checked inputs (fp32 ``verts [V, 3]``, int32 ``faces [F, 3]``, fp32
+    ``origins`` / ``dirs [R, 3]``, all contiguous on one device): ``(t [R], face [R] int32,
+    bary [R, 3] or None, flag [1] int32)``; ``flag`` is the device word a clamped face index
+    raises."""
+    capi.require_device(verts, faces, origins, dirs)
+    _contig(verts, faces, origins, dirs)
+    _f32(verts, origins, dirs)
+    dev = origins.device
+    V, F, R = verts.shape[0], faces.shape[0], origins.shape[0]
+    t = torch.empty(R, device=dev, dtype=torch.float32)
+    face = torch.empty(R, device=dev, dtype=torch.int32)
+    bary = torch.empty(R, 3, device=dev, dtype=torch.float32) if want_bary else None
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    if R > 0:
+        lib = capi.load()
+        ws = torch.empty(lib.ldm_ray_mesh_ws_bytes(F, R), device=dev, dtype=torch.uint8)
+        with torch.cuda.device(dev):
+            capi.check(lib.ldm_ray_mesh(capi.ptr(verts), V, capi.ptr(faces), F,
+                                        capi.ptr(origins), capi.ptr(dirs), R, float(t_min),
+                                        float(t_max), capi.ptr(t), capi.ptr(face),
+                                        capi.ptr(bary), capi.ptr(flag), capi.ptr(ws), ws.numel(),
+                                        capi.stream_handle(dev)), "ldm_ray_mesh")
+    return t, face, bary, flag
