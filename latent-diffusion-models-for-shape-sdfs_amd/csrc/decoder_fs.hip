@@ -23,8 +23,7 @@
 //       - a layer's part 0 (set A) -> the "early" positions 0..15, during the SAME layer's
 //         part 1 steps 16-30: part 1 reads the early positions in steps 0-15, so after the
 //         barrier inside its step 15 no wave reads them any more; the barrier inside its
-//         step 31 publishes them to the next layer (layer 1 converts ahead instead, in its
-//         part 1's plain steps 8-15, and writes in steps 16-19: run_part);
+//         step 31 publishes them to the next layer;
 //       - layer 7's parts fold into the final 512 -> 1 dot product instead (fp32, w_last):
 //         part 0 during part 1, part 1 during the NEXT tile's layer 1 part 0 (which also
 //         stores the previous tile's outputs).
@@ -126,19 +125,18 @@ struct FArgs {
     GridDiv gd;              // grid mode: the reciprocals of N (grid_index.h)
 };
 
-// Epilogue kinds run inside 8 k-steps of a part (on the OTHER accumulator set)
+// Epilogue kinds run inside a 16-step window of a part (on the OTHER accumulator set), every
+// step of it hand-ordered (window_step, window_step_fin).  Every element is read out of the
+// accumulator file at its use, as an "a" operand of a pair block: as plain values the register
+// allocator copied the finished set into VGPRs in one burst at the part's start, with the
+// matrix pipe idle (and the set FE_FIN1 folds, carried around the tile loop, at the loop header:
+// DESIGN.md §4 "tile prologue").
+//   FE_LATE / FE_EARLY: a layer's part 1 / part 0 -> the late / early positions (16-bit, ReLU)
 //   FE_FIN0: layer 7 part 0 (set A) -> the final dot product, during layer 7 part 1;
 //   FE_FIN1: layer 7 part 1 of the PREVIOUS tile (set B) -> the dot product, during layer 1 part
 //            0 of this one; its step 14 publishes the partials (the mid barrier) and the part
 //            sums them and stores the previous tile's outputs after that barrier
-//   FE_CVT / FE_WR: the two halves of an unpinned FE_EARLY in a 32-step part (run_part, the
-//            "ahead" form, layer 1 part 1 only): the set is converted into VGPR fragments during
-//            the plain steps 8-15 and written out in steps 16-19
-// FE_PIN (a flag on FE_LATE / FE_EARLY / FE_FIN0): read every element through acc_read() at its
-// use (FE_FIN1 always does).  Which sites carry it is decided per site from the assembly, see the
-// table at the call sites in dec_fs_kernel.
-enum FsEpi { FE_NONE = 0, FE_LATE = 1, FE_EARLY = 2, FE_FIN0 = 3, FE_FIN1 = 4, FE_CVT = 5,
-             FE_WR = 6, FE_PIN = 8 };
+enum FsEpi { FE_NONE = 0, FE_LATE = 1, FE_EARLY = 2, FE_FIN0 = 3, FE_FIN1 = 4 };
 
 // A fragment source: a buffer resource (SGPRs) + a byte offset (SGPR); the lane's 16 bytes at
 // voffset lane*16 (+1024: the second fragment, an immediate).  Raw buffer loads keep every
@@ -165,7 +163,8 @@ struct FCtx {
     u32x4 ring[kFsD][2];
     u32x4 b[4];               // the B fragments of the step about to run (rolling)
     float part[4];            // final-layer partial sums of point chunk n
-    u32x4 ef[16];             // FE_CVT -> FE_WR: the finished set as fragments, [tile 4i + n][s]
+    const f32x4* wlp;         // FE_FIN0 / FE_FIN1 window: this lane's final-layer weights (wl_at)
+    f32x4 wl[2][4];           // ... of m-chunk i, as registers (window_step_fin)
     float* out;               // the previous tile's outputs (FE_FIN1): [shape][npts]
     int npts, prev_shape, prev_local;   // prev_local < 0: no previous tile
     float b_last;
@@ -214,6 +213,15 @@ __device__ __forceinline__ int opaque_s(int v) {
 __device__ __forceinline__ char* lds_at(const FCtx& c, uint32_t off) {
     return c.smem + (opaque(c.voff) + off);
 }
+// A group base: the SUM is opaque as well, so that what a group adds to it (< 16 KiB) stays in
+// the ds_read / ds_write immediates.  Between asm statements the compiler otherwise folds each
+// access's offset into the constant and spends one v_add per access past 64 KiB.
+__device__ __forceinline__ char* lds_base(const FCtx& c, uint32_t off) {
+    return c.smem + opaque(opaque(c.voff) + off);
+}
+__device__ __forceinline__ u32x4* act_wb(const FCtx& c, int late) {
+    return reinterpret_cast<u32x4*>(lds_base(c, (uint32_t)(late + 4 * c.wave) * 4096u));
+}
 // this wave's early (0) / late (16) positions: + (2i + s) * 4 KiB + n * 1 KiB immediates
 __device__ __forceinline__ u32x4* act_w(const FCtx& c, int late) {
     return reinterpret_cast<u32x4*>(lds_at(c, (uint32_t)(late + 4 * c.wave) * 4096u));
@@ -260,10 +268,11 @@ __device__ __forceinline__ void issue(FCtx& c, int r) {
     c.ring[r][1] = bld(c.rw, vo + 1024u, so);
 }
 
-__device__ __forceinline__ void next_group(FCtx& c) {
-    c.s_iss += 4u * kFsStep;
-    if (c.s_iss == c.s_end) c.s_iss = c.s_beg;
+__device__ __forceinline__ uint32_t next_iss(const FCtx& c) {
+    const uint32_t n = c.s_iss + 4u * kFsStep;
+    return n == c.s_end ? c.s_beg : n;
 }
+__device__ __forceinline__ void next_group(FCtx& c) { c.s_iss = next_iss(c); }
 
 // ReLU of an fp32 value as ONE integer max: a negative float is a negative int32 (sign bit),
 // so max(bits, 0) is +0 for it and the value itself otherwise (fmaxf costs a NaN-quieting
@@ -272,105 +281,177 @@ __device__ __forceinline__ float relu_f(float x) {
     return __builtin_bit_cast(float, max(__builtin_bit_cast(int, x), 0));
 }
 
-// One element of the set FE_FIN1 folds, read out of the accumulator file AT ITS USE.  That set
-// is carried around the tile loop (layer 7 part 1 of the previous tile), and as a plain value
-// the register allocator split it at the loop header: 128 v_accvgpr_read there, with the matrix
-// pipe idle, and 128 VGPRs held across layer 0 (DESIGN.md §4 "tile prologue").  An EMPTY asm
-// statement with the element as an "a" operand pins it to the accumulator file up to this
-// point; the v_accvgpr_read that follows is the compiler's own, so it fills the step's VALU
-// slots and gets its wait states like any other.  (One pin of the whole set after layer 0
-// instead made the allocator shuffle 64 registers through v_accvgpr_mov / _write; a pin per
-// element at its use adds no instruction.)
+// One element of layer 7 part 1 in the drain after the tile loop, read out of the accumulator
+// file AT ITS USE: an EMPTY asm statement with the element as an "a" operand pins it there up to
+// this point, as the pair blocks' operands do inside the loop (the set is carried around the
+// tile loop; one pin of the whole set instead made the allocator shuffle 64 registers through
+// v_accvgpr_mov / _write).
 __device__ __forceinline__ float acc_read(float a) {
     asm volatile("" : "+a"(a));
     return a;
 }
 
-// One epilogue unit u = 2t + s of the other accumulator set: HALF of tile t = 4i + n (its
-// accumulator registers 8s..8s+7 = the B fragment of k-step 2i + s).
-// `wbase`: this wave's early / late positions (act_w), formed once per 4-step group.
-template <typename T, int EKP>
-__device__ __forceinline__ void epi_unit(FCtx& c, const f32x16 (&accY)[2][4], int u,
-                                         u32x4* wbase) {
-    constexpr int EK = EKP & 7;
-    constexpr bool PIN = (EKP & FE_PIN) != 0 || EK == FE_FIN1;
+// One FE_FIN1 unit u = 2t + s outside a window (the drain of the workgroup's last tile): HALF
+// of tile t = 4i + n (its accumulator registers 8s..8s+7) folded into c.part[n].  The elements,
+// their order and the chain per n are window_step_fin's.
+__device__ __forceinline__ void fin1_unit(FCtx& c, const f32x16 (&accY)[2][4], int u) {
     const int t = u >> 1, s = u & 1;
     const int i = t >> 2, n = t & 3;
-    if (FS_ABL & 2) return;
-    if (EK == FE_LATE || EK == FE_EARLY) {   // part 1 of the previous layer / part 0 of this
-        u32x4 f;
+    const f32x4* w = wl_at(c, 1, i);
+    float part = c.part[n];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float lo = accY[i][n][8 * s + 2 * q], hi = accY[i][n][8 * s + 2 * q + 1];
-            f[q] = relu2(PIN ? Elem<T>::pack(acc_read(lo), acc_read(hi)) : Elem<T>::pack(lo, hi));
-        }
-        wbase[((2 * i + s) * 4 + n) * 64] = f;
-    } else if (EK == FE_FIN0 || EK == FE_FIN1) {     // layer 7 -> the final dot product
-        const f32x4* w = wl_at(c, EK == FE_FIN0 ? 0 : 1, i);
-        float part = c.part[n];
+    for (int q = 2 * s; q < 2 * s + 2; ++q) {
+        const f32x4 wv = w[q];
 #pragma unroll
-        for (int q = 2 * s; q < 2 * s + 2; ++q) {
-            const f32x4 wv = w[q];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float v = PIN ? acc_read(accY[i][n][4 * q + e]) : accY[i][n][4 * q + e];
-                part = fmaf(relu_f(v), wv[e], part);
-            }
-        }
-        c.part[n] = part;
+        for (int e = 0; e < 4; ++e)
+            part = fmaf(relu_f(acc_read(accY[i][n][4 * q + e])), wv[e], part);
     }
+    c.part[n] = part;
 }
 
-// The 16 units of an epilogue window of 16 steps k = 0..15: unit k in step k < 14, units 14
-// and 15 in step 14, none in step 15 -- so the window's LDS writes are all issued before the
-// barrier that closes it (inside step 15, see group4).
-//
-// The ahead form of FE_EARLY (k = 0..7 / 0..3 here): FE_CVT step k converts tile k = 4i + n
-// (16 reads, 8 conversions, 8 ReLUs) into c.ef, FE_WR step k writes tiles 2k and 2k + 1.
-template <typename T, int EKP>
-__device__ __forceinline__ void epi_step(FCtx& c, const f32x16 (&accY)[2][4], int k,
-                                         u32x4* wbase) {
-    constexpr int EK = EKP & 7;
-    if (EK == FE_NONE || k == 15) return;
-    if (EK == FE_CVT) {
-        if ((FS_ABL & 2) || k >= 8) return;
-        u32x4 f0, f1;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x16& a = accY[k >> 2][k & 3];
-            f0[q] = relu2(Elem<T>::pack(acc_read(a[2 * q]), acc_read(a[2 * q + 1])));
-            f1[q] = relu2(Elem<T>::pack(acc_read(a[8 + 2 * q]), acc_read(a[8 + 2 * q + 1])));
-        }
-        c.ef[2 * k] = f0;
-        c.ef[2 * k + 1] = f1;
-        return;
-    }
-    if (EK == FE_WR) {
-        if ((FS_ABL & 2) || k >= 4) return;
-#pragma unroll
-        for (int t = 2 * k; t < 2 * k + 2; ++t) {
-            const int i = t >> 2, n = t & 3;
-            wbase[(2 * i * 4 + n) * 64] = c.ef[2 * t];
-            wbase[((2 * i + 1) * 4 + n) * 64] = c.ef[2 * t + 1];
-        }
-        return;
-    }
-    epi_unit<T, EKP>(c, accY, k, wbase);
-    if (k == 14) epi_unit<T, EKP>(c, accY, 15, wbase);
-    if (EK == FE_FIN0 && k == 14) {
-        // the partial sums are next used in the next tile: fix them HERE, or the whole chain of
-        // FMAs is sunk below the part's plain steps and its 128 inputs are kept (and spilled)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) asm volatile("" : "+v"(c.part[n]));
-    }
-    if (EK == FE_FIN1 && k == 14) {         // the partials -> red[wave][n][lane], published by
-        float* rw = red_w(c);               // the barrier inside step 15
+// MFMA pair of point chunk n of one step (both m-chunks of the wave's part)
+template <typename T>
+__device__ __forceinline__ void mfma_pair(f32x16 (&acc)[2][4], const u32x4& a0, const u32x4& a1,
+                                          const u32x4& b, int n) {
+    acc[0][n] = Elem<T>::mfma(a0, b, acc[0][n]);
+    acc[1][n] = Elem<T>::mfma(a1, b, acc[1][n]);
+}
+
+// Step k < 15 of an FE_LATE / FE_EARLY window, hand-ordered: the step's four MFMA pairs as pair
+// blocks (decoder_common.h) that carry unit k's conversion -- elements 8s + 2n, 8s + 2n + 1 of
+// its half tile behind pair n -- with the memory operations between them, each held in its MFMA
+// gap by a sched_barrier: chunk n's next B read behind pair n, the step's two weight loads and
+// the unit's write behind the last.  Per gap: 2 VALU | 2 VALU + the read; the last pair 4 VALU |
+// none, so the step's tail holds 4 instructions (read, two loads, write).  Step 14 carries units
+// 14 and 15 = the 16 elements of tile (1, 3): pair p converts elements 4p .. 4p + 3 (4 | 4 VALU,
+// 6 | 2 in the last), so unit 14's fragment is written behind pair 1 already.
+// `nb`: the next position's B fragments (group4's base + immediates).
+template <typename T>
+__device__ __forceinline__ void window_step(FCtx& c, f32x16 (&acc)[2][4],
+                                            const f32x16 (&accY)[2][4], const u32x4& a0,
+                                            const u32x4& a1, const u32x4* nb, int k, int r,
+                                            u32x4* wbase) {
+    // the group's last step: the next group's ring offset (next_group) behind the first pair
+    uint32_t nxt = 0;
+    if (k < 14) {
+        const int t = k >> 1, s = k & 1;
+        const int i = t >> 2, nn = t & 3;
+        u32x4 f;
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
-            rw[n * 64] = c.part[n];
-            c.part[n] = 0.f;
+            unsigned w;
+            if (r == 3 && n == 1) nxt = next_iss(c);
+            const float e0 = accY[i][nn][8 * s + 2 * n], e1 = accY[i][nn][8 * s + 2 * n + 1];
+            if (n < 3)
+                Elem<T>::template pair_cvt1<false>(acc[0][n], acc[1][n], a0, a1, c.b[n], e0, e1,
+                                                   w);
+            else
+                Elem<T>::template pair_cvt1<true>(acc[0][n], acc[1][n], a0, a1, c.b[n], e0, e1,
+                                                  w);
+            f[n] = w;
+            c.b[n] = nb[n * 64];
+            __builtin_amdgcn_sched_barrier(0);
         }
+        issue(c, r);
+        wbase[((2 * i + s) * 4 + nn) * 64] = f;
+        if (r == 3) c.s_iss = nxt;
+    } else {
+        u32x4 f[2];
+        const f32x16& y = accY[1][3];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            unsigned w0, w1;
+            if (p < 3)
+                Elem<T>::template pair_cvt2<false>(acc[0][p], acc[1][p], a0, a1, c.b[p], y[4 * p],
+                                                   y[4 * p + 1], y[4 * p + 2], y[4 * p + 3], w0,
+                                                   w1);
+            else
+                Elem<T>::template pair_cvt2<true>(acc[0][p], acc[1][p], a0, a1, c.b[p], y[4 * p],
+                                                  y[4 * p + 1], y[4 * p + 2], y[4 * p + 3], w0,
+                                                  w1);
+            f[p >> 1][2 * (p & 1)] = w0;
+            f[p >> 1][2 * (p & 1) + 1] = w1;
+            c.b[p] = nb[p * 64];
+            if (p == 1) wbase[(2 * 4 + 3) * 64] = f[0];
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        issue(c, r);
+        wbase[(3 * 4 + 3) * 64] = f[1];
     }
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// Step k < 15 of an FE_FIN0 (P = 0) / FE_FIN1 (P = 1) window, hand-ordered like window_step:
+// pair n folds elements 8s + 2n, 8s + 2n + 1 of unit k < 14 into c.part (fin1_unit's elements,
+// order and chain).  Three VALU an element leave no room for a double-unit step, so the 16
+// elements y of tile (1, 3) -- units 14 and 15, the end of chain 3, whose earlier units are 6 and
+// 7 -- ride behind the first two pairs of steps 8-13, one each (y[2 (k - 8) + n], pair_fin3), and
+// of step 14, two each; chain 3 keeps its order, and the other chains never meet it.
+// The final-layer weights of an m-chunk (4 x 16 bytes a lane) are read once per window instead
+// of 32 bytes per step: chunk 0's ahead of the window's first block, chunk 1's one fragment
+// behind each pair of step 6.  The ring's wrap test of a group's last step stands behind pair 2
+// here (pairs 0-1 carry the extra element in steps 8-13).
+template <typename T, int P>
+__device__ __forceinline__ void window_step_fin(FCtx& c, f32x16 (&acc)[2][4],
+                                                const f32x16 (&accY)[2][4], const u32x4& a0,
+                                                const u32x4& a1, const u32x4* nb, int k, int r) {
+    const int t = k >> 1, s = k & 1;
+    const int i = t >> 2, nn = t & 3;
+    const f32x16& y = accY[1][3];
+    uint32_t nxt = 0;
+    if (k == 0) {
+        c.wlp = wl_at(c, P, 0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) c.wl[0][q] = c.wlp[q];
+    }
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        if (k < 14) {
+            const int e = 8 * s + 2 * n;
+            const float e0 = accY[i][nn][e], e1 = accY[i][nn][e + 1];
+            const float w0 = c.wl[i][e >> 2][e & 3], w1 = c.wl[i][e >> 2][(e & 3) + 1];
+            const int x = 2 * (k - 8) + n;
+            if (k >= 8 && n < 2)
+                Elem<T>::pair_fin3(acc[0][n], acc[1][n], a0, a1, c.b[n], e0, e1, w0, w1,
+                                   c.part[nn], y[x], c.wl[1][x >> 2][x & 3], c.part[3]);
+            else if (n < 3)
+                Elem<T>::template pair_fin<false>(acc[0][n], acc[1][n], a0, a1, c.b[n], e0, e1,
+                                                  w0, w1, c.part[nn]);
+            else
+                Elem<T>::template pair_fin<true>(acc[0][n], acc[1][n], a0, a1, c.b[n], e0, e1,
+                                                 w0, w1, c.part[nn]);
+        } else if (n < 2) {
+            const int x = 12 + 2 * n;
+            Elem<T>::template pair_fin<false>(acc[0][n], acc[1][n], a0, a1, c.b[n], y[x],
+                                              y[x + 1], c.wl[1][3][x & 3],
+                                              c.wl[1][3][(x & 3) + 1],
+                                              c.part[3]);
+        } else {
+            mfma_pair<T>(acc, a0, a1, c.b[n], n);
+        }
+        if (r == 3 && n == 2) nxt = next_iss(c);
+        c.b[n] = nb[n * 64];
+        if (k == 6) c.wl[1][n] = c.wlp[8 + n];    // m-chunk 1: + 128 bytes
+        if (k == 14 && n == 2) {
+            if (P == 0) {
+                // the partial sums are next used in the next tile: fixed HERE, as they were
+                // when the chain was compiled code (otherwise sunk below the part's plain steps)
+#pragma unroll
+                for (int m = 0; m < 4; ++m) asm volatile("" : "+v"(c.part[m]));
+            } else {                        // the partials -> red[wave][n][lane], published by
+                float* rw = red_w(c);       // the barrier inside step 15
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    rw[m * 64] = c.part[m];
+                    c.part[m] = 0.f;
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    issue(c, r);
+    if (r == 3) c.s_iss = nxt;
+    __builtin_amdgcn_sched_barrier(0);
 }
 
 // the final layer across waves and lane halves (lanes l and l^32 hold the same point): lanes
@@ -457,20 +538,6 @@ __device__ __forceinline__ void fin_store_mode(const FCtx& c) {
     else fin_store(c, c.prev_shape, c.prev_local);
 }
 
-// scheduling slot of v VALU instructions (0, 2 or 4; v is a constant once unrolled)
-__device__ __forceinline__ void valu_slot(int v) {
-    if (v == 2) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-    else if (v == 4) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-}
-
-// MFMA pair of point chunk n of one step (both m-chunks of the wave's part)
-template <typename T>
-__device__ __forceinline__ void mfma_pair(f32x16 (&acc)[2][4], const u32x4& a0, const u32x4& a1,
-                                          const u32x4& b, int n) {
-    acc[0][n] = Elem<T>::mfma(a0, b, acc[0][n]);
-    acc[1][n] = Elem<T>::mfma(a1, b, acc[1][n]);
-}
-
 // Four k-steps reading positions p0..p0+3 (ring slots 0..3), epilogue window steps K0..K0+3.
 // Rolling B fragments: chunk n of step j+1 is read as soon as step j's two MFMAs on chunk n are
 // issued (~6 MFMAs, ~190 cycles, before it is needed).  BAR = r: an LDS barrier INSIDE step r,
@@ -478,29 +545,38 @@ __device__ __forceinline__ void mfma_pair(f32x16 (&acc)[2][4], const u32x4& a0, 
 // the waves wait on each other with the step's remaining MFMAs still to issue and the next
 // position's reads still covered by them (a barrier between steps exposed one LDS round trip
 // plus the pipeline drain, ~500-750 cycles per barrier).
-template <typename T, int EKP, int K0, int BAR>
+// Steps 0-14 of a window (EK != FE_NONE) are hand-ordered (window_step, window_step_fin); its
+// step 15 carries no unit and runs, like a plain group's steps, as compiled code whose order the
+// sched_group_barriers pin.  A window's groups get their bases from steps16e (WIN: `gb` for the
+// reads, `wb` for the units' writes), a plain group forms its read base here.
+// `go` (steps_plain's rolled loop): the group's read base as an LDS offset carried from group to
+// group, one position BELOW the group's first read.  It is advanced by a group in the first gap
+// of the group's last step, whose own reads then take it with immediates from 0 (so the old
+// value is dead and the add is in place), and the ring's wrap test stands in that gap as well:
+// behind the group's last MFMA only that step's B read, its two weight loads and the loop's own
+// add / compare / branch remain.
+template <typename T, int EK, int K0, int BAR, bool WIN = false>
 __device__ __forceinline__ void group4(FCtx& c, f32x16 (&acc)[2][4], const f32x16 (&accY)[2][4],
-                                       int p0) {
-    constexpr int EK = EKP & 7;
+                                       int p0, const char* gb = nullptr, u32x4* wb = nullptr,
+                                       uint32_t* go = nullptr) {
+    static_assert(WIN || EK == FE_NONE, "windows run through steps16e");
     constexpr int BP = 1;                    // MFMA pairs before the in-stream barrier
-    // likewise ONE base for the group's epilogue writes (the unit's position is an immediate);
-    // formed per unit it cost v_mov + s_nop + v_add in steps that are issue-bound
-    u32x4* wbase = nullptr;
-    if (EK == FE_LATE) wbase = act_w(c, 16);
-    if (EK == FE_EARLY || EK == FE_WR) wbase = act_w(c, 0);
+    const bool carry = go != nullptr;        // (a constant once inlined: &local or nullptr)
     // ONE LDS base for the group's four next positions (r * 4 KiB + n * 1 KiB fold into the
     // ds_read immediates) instead of an address formed per step
-    const char* gbase = lds_at(c, (p0 + 1) * 4096);
+    const char* gbase = WIN ? gb : carry ? c.smem + *go + 4096 : lds_base(c, (p0 + 1) * 4096);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const u32x4* nb = reinterpret_cast<const u32x4*>(gbase + r * 4096);
+        const bool last = carry && r == 3;
+        uint32_t nxt = 0;
+        if (last) {
+            nxt = next_iss(c);
+            *go = opaque(*go + 4u * 4096u);
+        }
+        const u32x4* nb =
+            reinterpret_cast<const u32x4*>(last ? c.smem + *go : gbase + r * 4096);
         const u32x4 a0 = c.ring[r][0], a1 = c.ring[r][1];
         const int k = K0 + r;
-        // the step's VALU (epilogue: AGPR reads, cvt, ReLU, LDS address) 2 per MFMA gap, 4 in
-        // the double-unit step 14 (the guide: <= 5 fillers per 32x32x16 gap hide)
-        // (FE_CVT: 32 VALU a step, in steps that carry nothing else)
-        const int V = (EK == FE_NONE || EK == FE_WR || k == 15) ? 0
-                      : (k == 14 || EK == FE_CVT) ? 4 : 2;
         if (r == BAR) {
 #pragma unroll
             for (int n = 0; n < BP; ++n) mfma_pair<T>(acc, a0, a1, c.b[n], n);
@@ -518,15 +594,19 @@ __device__ __forceinline__ void group4(FCtx& c, f32x16 (&acc)[2][4], const f32x1
                 c.b[n] = nb[n * 64];
             }
             issue(c, r);
-            epi_step<T, EKP>(c, accY, k, wbase);
             for (int n = 0; n < BP; ++n) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             for (int n = BP; n < 4; ++n) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                valu_slot(V);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                valu_slot(V);
             }
+        } else if ((EK == FE_LATE || EK == FE_EARLY) && k < 15 && !(FS_ABL & 2)) {
+            window_step<T>(c, acc, accY, a0, a1, nb, k, r, wb);
+            if (r == 3) return;      // the ring's wrap test went into the step (window_step)
+            continue;
+        } else if ((EK == FE_FIN0 || EK == FE_FIN1) && k < 15 && !(FS_ABL & 2)) {
+            window_step_fin<T, EK == FE_FIN1>(c, acc, accY, a0, a1, nb, k, r);
+            if (r == 3) return;
+            continue;
         } else {
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
@@ -534,23 +614,24 @@ __device__ __forceinline__ void group4(FCtx& c, f32x16 (&acc)[2][4], const f32x1
                 c.b[n] = nb[n * 64];
             }
             issue(c, r);
-            epi_step<T, EKP>(c, accY, k, wbase);
+            if (last) c.s_iss = nxt;
             // pin the step's order for the scheduler (left free it sank the B reads and weight
-            // loads below the last MFMA): per point chunk n, MFMA, [VALU], MFMA, B read,
-            // [VALU]; then the 2 weight loads
+            // loads below the last MFMA): per point chunk n, 2 MFMAs, B read; then the 2 weight
+            // loads
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                valu_slot(V);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+                if (last && n == 0) {
+                    __builtin_amdgcn_sched_group_barrier(0x004, 3, 0);    // add, compare, select
+                    __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);    // the next base
+                }
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                valu_slot(V);
             }
         }
         __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
-    next_group(c);
+    if (!carry) next_group(c);
 }
 
 // 16 k-steps from position p0 carrying the 16 epilogue units of the other set; BAR: the
@@ -558,10 +639,15 @@ __device__ __forceinline__ void group4(FCtx& c, f32x16 (&acc)[2][4], const f32x1
 template <typename T, int EK, bool BAR>
 __device__ __forceinline__ void steps16e(FCtx& c, f32x16 (&acc)[2][4],
                                          const f32x16 (&accY)[2][4], int p0) {
-    group4<T, EK, 0, -1>(c, acc, accY, p0);
-    group4<T, EK, 4, -1>(c, acc, accY, p0 + 4);
-    group4<T, EK, 8, -1>(c, acc, accY, p0 + 8);
-    group4<T, EK, 12, BAR ? 3 : -1>(c, acc, accY, p0 + 12);
+    // one base each for the window's 16 next positions (the last immediate is 15 * 4 KiB + 3 KiB
+    // < 64 KiB) and its 16 writes: formed per group they stood, with the ring's wrap test, in the
+    // gap behind the group's last MFMA, beside that step's B read, weight loads and write
+    const char* gb = lds_base(c, (p0 + 1) * 4096);
+    u32x4* wb = EK == FE_LATE ? act_wb(c, 16) : EK == FE_EARLY ? act_wb(c, 0) : nullptr;
+    group4<T, EK, 0, -1, true>(c, acc, accY, p0, gb, wb);
+    group4<T, EK, 4, -1, true>(c, acc, accY, p0 + 4, gb + 4 * 4096, wb);
+    group4<T, EK, 8, -1, true>(c, acc, accY, p0 + 8, gb + 8 * 4096, wb);
+    group4<T, EK, 12, BAR ? 3 : -1, true>(c, acc, accY, p0 + 12, gb + 12 * 4096, wb);
 }
 
 // plain k-steps [j0, j1) from position pos0 as ONE runtime loop of 4-step groups (code size:
@@ -569,8 +655,11 @@ __device__ __forceinline__ void steps16e(FCtx& c, f32x16 (&acc)[2][4],
 template <typename T>
 __device__ __forceinline__ void steps_plain(FCtx& c, f32x16 (&acc)[2][4],
                                             const f32x16 (&accY)[2][4], int pos0, int j0, int j1) {
+    if (j0 >= j1) return;
+    uint32_t go = opaque(opaque(c.voff) + (uint32_t)(pos0 + j0) * 4096u);
 #pragma unroll 1
-    for (int j = j0; j < j1; j += 4) group4<T, FE_NONE, 0, -1>(c, acc, accY, pos0 + j);
+    for (int j = j0; j < j1; j += 4)
+        group4<T, FE_NONE, 0, -1>(c, acc, accY, pos0 + j, nullptr, nullptr, &go);
 }
 
 // One part: the aux step, then nk ring steps reading positions pos0 .. pos0 + nk - 1 = 31
@@ -580,19 +669,15 @@ __device__ __forceinline__ void steps_plain(FCtx& c, f32x16 (&acc)[2][4],
 //     `bar0`, after a barrier (the part follows serial LDS writes: layers 1 and 4 at skip 253);
 //     then it loads the NEXT part's aux A fragments (naux).
 //   * E work (the other set, EK) in steps 0-15 (E16 false) or, E16 (FE_EARLY of a 32-step
-//     part), in steps 16-31 with FE_PIN.  E16 without FE_PIN is the ahead form: converted in
-//     the plain steps 8-15 (FE_CVT) and written in steps 16-19 (FE_WR), steps 20-27 a rolled
-//     loop again.  Only layer 1 part 1 uses it: pinned in its window it cost the bf16 skip-253
-//     instances 160 v_accvgpr_mov / _write.
+//     part), in steps 16-31.
 //   * `mid`: the barrier inside step 15 (the late positions written during steps 0-14 by
 //     every wave / no wave reads the early positions any more before E16 writes them);
 //     `endbar` (E work parts): the barrier inside the part's last step, publishing the window's
 //     writes to the next part, whose aux step then reads on without a barrier.
-template <typename T, int EKP, bool E16, int MODE = kModeGrid>
+template <typename T, int EK, bool E16, int MODE = kModeGrid>
 __device__ __forceinline__ void run_part(FCtx& c, f32x16 (&acc)[2][4], const f32x16 (&accY)[2][4],
                                          int nk, bool mid, bool endbar, FSrc naux, int pos0,
                                          bool bar0) {
-    constexpr int EK = EKP & 7;
     const f32x16 zero = {};
     const u32x4 a0 = c.auxn[0], a1 = c.auxn[1];
     if (bar0) {
@@ -637,8 +722,8 @@ __device__ __forceinline__ void run_part(FCtx& c, f32x16 (&acc)[2][4], const f32
     stamp(c);
     if (!E16 && EK != FE_NONE) {        // E work in steps 0-15
         // the barrier inside step 15: mid (nk 32), or the end barrier of a 16-step part
-        if (mid || (endbar && nk == 16)) steps16e<T, EKP, true>(c, acc, accY, pos0);
-        else steps16e<T, EKP, false>(c, acc, accY, pos0);
+        if (mid || (endbar && nk == 16)) steps16e<T, EK, true>(c, acc, accY, pos0);
+        else steps16e<T, EK, false>(c, acc, accY, pos0);
         if (EK == FE_FIN1) {
             stamp(c);
             fin_store_mode<MODE>(c);
@@ -650,21 +735,13 @@ __device__ __forceinline__ void run_part(FCtx& c, f32x16 (&acc)[2][4], const f32
         } else {
             steps_plain<T>(c, acc, accY, pos0, 16, nk);
         }
-    } else if (E16 && (EKP & FE_PIN)) {     // nk 32, mid: the window in steps 16-31
+    } else if (E16) {                   // nk 32, mid: the window in steps 16-31
+        static_assert(!E16 || EK == FE_EARLY, "E16 parts convert part 0 of their own layer");
         steps_plain<T>(c, acc, accY, pos0, 0, 12);
         group4<T, FE_NONE, 0, 3>(c, acc, accY, pos0 + 12);
         stamp(c);
-        if (endbar) steps16e<T, EKP, true>(c, acc, accY, pos0 + 16);
-        else steps16e<T, EKP, false>(c, acc, accY, pos0 + 16);
-    } else if (E16) {                   // nk 32, mid, endbar, FE_EARLY unpinned: the ahead form
-        static_assert(!E16 || EK == FE_EARLY, "E16 parts convert part 0 of their own layer");
-        steps_plain<T>(c, acc, accY, pos0, 0, 8);
-        group4<T, FE_CVT, 0, -1>(c, acc, accY, pos0 + 8);
-        group4<T, FE_CVT, 4, 3>(c, acc, accY, pos0 + 12);
-        stamp(c);
-        group4<T, FE_WR, 0, -1>(c, acc, accY, pos0 + 16);
-        steps_plain<T>(c, acc, accY, pos0, 20, 28);
-        group4<T, FE_NONE, 0, 3>(c, acc, accY, pos0 + 28);
+        if (endbar) steps16e<T, EK, true>(c, acc, accY, pos0 + 16);
+        else steps16e<T, EK, false>(c, acc, accY, pos0 + 16);
     } else {                            // plain part, no barrier (layer 4 part 0 at skip 253)
         steps_plain<T>(c, acc, accY, pos0, 0, nk < 16 ? nk : 16);
         stamp(c);
@@ -890,16 +967,10 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
 
         // ---- two-part layers 1, 2 (and 3 when 512 wide).  L1p0 folds the previous tile's
         // layer 7 part 1 into its outputs (FE_FIN1); p1 of layer l publishes with its end barrier.
-        // FE_PIN per site, from the assembly of all 12 instances (tests/
-        // test_decoder_window_codegen.py).  Without it the allocator copies the finished set
-        // into VGPRs in one burst at the part's start, with the matrix pipe idle; with it on a
-        // site that needs none it shuffles accumulators (v_accvgpr_mov / _write) instead.  The
-        // windows of layers 5, 6 and 7 part 0, of layer 7 part 1 (FE_FIN0), of layer 4 part 1
-        // at skip 253 and of every part 1 from layer 2 on carry it (layer 1 part 1 converts
-        // ahead, see run_part); those of layer 2 (and 3) part 0 and the last one before layer
-        // 4 only in the regular 512-wide layer order (at skip 253, where layer 3 is one part,
-        // they read in place as they are and the pin costs 368 moves).
-        constexpr int kPinW = S == 512 ? FE_PIN : 0;
+        // Every window reads its set in place, through the "a" operands of its pair blocks: no
+        // instance shuffles accumulators for it (tests/test_decoder_window_codegen.py), the
+        // windows of layer 2 (and 3) part 0 at skip 253 and of layer 1 part 1 included, where
+        // pins on compiled conversions once cost 368 and 160 v_accvgpr_mov / _write.
         int pi = 2;
         run_part<T, FE_FIN1, false, MODE>(c, accA, accB, 32, true, false, bias(pi + 1), 0, true);
         run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0, false);
@@ -909,45 +980,45 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
         for (int l = 2; l < L2P; ++l, pi += 2) {
             // the part after layer 3 (512 wide) is layer 4's: per-shape aux
             const FSrc nx = (S == 512 && l == 3) ? shp(2) : bias(pi + 2);
-            run_part<T, FE_LATE | kPinW, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0,
+            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0,
                                                 false);
-            run_part<T, FE_EARLY | FE_PIN, true>(c, accB, accA, 32, true, true, nx, 0, false);
+            run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, nx, 0, false);
         }
         if (S == 256) {
             // layer 3: one part of rows 64w..64w+63 -> positions 16 + 4w + 2i + s (serial,
             // once every wave is done reading layer 3's inputs)
-            run_part<T, FE_LATE | kPinW, false>(c, accA, accB, 32, true, false, shp(2), 0,
+            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, shp(2), 0,
                                                 false);
             fs_bar();
             acc_to_lds<T>(c, accA);
             stamp(c);
             // layer 4 (K = 256, positions 16..31); part 0 -> early positions during part 1
             run_part<T, FE_NONE, false>(c, accA, accB, 16, false, false, shp(3), 16, true);
-            run_part<T, FE_EARLY | FE_PIN, false>(c, accB, accA, 16, false, true, bias(pi + 3),
+            run_part<T, FE_EARLY, false>(c, accB, accA, 16, false, true, bias(pi + 3),
                                                   16, false);
             pi += 3;
         } else {
-            run_part<T, FE_LATE | kPinW, false>(c, accA, accB, 32, true, false, shp(3), 0,
+            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, shp(3), 0,
                                                 false);
-            run_part<T, FE_EARLY | FE_PIN, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0,
+            run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0,
                                                  false);
             pi += 2;
         }
         // ---- layers 5, 6
 #pragma unroll 1
         for (int l = 5; l < 7; ++l, pi += 2) {
-            run_part<T, FE_LATE | FE_PIN, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0,
+            run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0,
                                                  false);
-            run_part<T, FE_EARLY | FE_PIN, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0,
+            run_part<T, FE_EARLY, true>(c, accB, accA, 32, true, true, bias(pi + 2), 0,
                                                  false);
         }
         // ---- layer 7: part 0 folds into the dot product during part 1, part 1 during the
         // next tile's L1p0 (its end barrier lets the next tile overwrite every position)
-        run_part<T, FE_LATE | FE_PIN, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0,
+        run_part<T, FE_LATE, false>(c, accA, accB, 32, true, false, bias(pi + 1), 0,
                                              false);
         // (no prefetch of the next tile's first aux fragments here: live across the whole
         // part they were spilled, each spill waiting for the whole ring)
-        run_part<T, FE_FIN0 | FE_PIN, false>(c, accB, accA, 32, false, true, FSrc{true, 0, true},
+        run_part<T, FE_FIN0, false>(c, accB, accA, 32, false, true, FSrc{true, 0, true},
                                              0, false);
         c.prev_shape = shape;
         c.prev_local = local;
@@ -956,7 +1027,7 @@ __global__ __launch_bounds__(256, 1) void dec_fs_kernel(FArgs a) {
     // the last tile's layer 7 part 1: the FE_FIN1 units in their window order (a point's
     // value must not depend on whether its tile was its workgroup's last)
 #pragma unroll
-    for (int u = 0; u < 16; ++u) epi_unit<T, FE_FIN1>(c, accB, u, nullptr);
+    for (int u = 0; u < 16; ++u) fin1_unit(c, accB, u);
     {
         float* rw = red_w(c);
 #pragma unroll
