@@ -286,6 +286,27 @@ int ldm_sample_loop_config(int form, unsigned spin_limit, int tagged);
  * LDM_LOOP_FLAT; 0 before any launch). */
 int ldm_sample_loop_last_form(void);
 
+/* The A10 loop for batches above 16 on the matrix cores (csrc/sample_batch.hip):
+ * the contract of ldm_sample_loop -- x fp32 [2][B][D] ping-pong with x[0] = x_T on entry, the
+ * result in x[steps & 1]; noise fp32 [T][B][D], noise[t] the z of step t, not read at t == 0;
+ * steps t_hi .. t_hi-steps+1 -- as one pack launch and 2 + n_blocks ordinary ldm_gemm_bf16
+ * launches per step, all enqueued by this one call on the caller's stream.  No grid barrier, no
+ * spin wait and so no status word; no synchronisation, allocation or host read of device data
+ * (the tables are read on the device at t): the call can be captured into a graph.
+ * Arithmetic (the training forward's): bf16 operands (x and every h rounded to bf16 where a
+ * product reads them), fp32 accumulation, fp32 residual stream, E_k[t] = e_tab[k] + t H as the
+ * block bias, fp32 x in the update.  Not bitwise equal to the B <= 16 kernels, which keep fp32
+ * activations.  A row's result does not depend on B nor on its position in the batch.
+ * Supported: dtype LDM_BF16 with e_tab[k] set, D and H multiples of 64, 1..LDM_MAX_BLOCKS
+ * blocks, 1 <= B <= 2^31 / max(D, H) rounded down to a multiple of 64 (LDM_ENOSYS above, and
+ * for LDM_F32).  Rows >= B of x and noise are never touched.  ws: ldm_sample_batch_ws_bytes(w,
+ * B) bytes (0 for an unsupported shape), 256-byte aligned (LDM_EALIGN; x and noise 16-byte);
+ * LDM_ENOSPC when ws_bytes is short; LDM_EINVAL for t_hi / steps outside the schedule. */
+int ldm_sample_batch_supported(const ldm_denoiser_t* w, int B);
+size_t ldm_sample_batch_ws_bytes(const ldm_denoiser_t* w, int B);
+int ldm_sample_batch(const ldm_denoiser_t* w, const ldm_sched_t* sc, float* x, const float* noise,
+                     int t_hi, int steps, int B, void* ws, size_t ws_bytes, ldm_stream_t s);
+
 /* ---- A6/A7/A9 training: denoiser forward with saved activations, backward, fused step ----
  * bf16 weights (w->dtype == LDM_BF16, the wt_* transposed copies set), matrix-core GEMMs
  * (ldm_gemm_bf16) with bf16 operands and fp32 accumulation, per-sample timesteps t int32 [B].

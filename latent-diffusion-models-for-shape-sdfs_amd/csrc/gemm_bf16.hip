@@ -48,6 +48,7 @@ struct GemmKArgs {
     int nk[LDM_GEMM_MAX_PROBS];         // k-steps per tile (per slice when split)
     int ksplit[LDM_GEMM_MAX_PROBS];     // slices (1: whole K)
     ldm_gemm_prob_t prob[LDM_GEMM_MAX_PROBS];
+    DdpmEpi step;                       // STEP kernels only (gemm_bf16_ddpm): problem 0's epilogue
 };
 typedef const __attribute__((address_space(4))) GemmKArgs KArgs;
 typedef const __attribute__((address_space(4))) ldm_gemm_prob_t KProb;
@@ -107,7 +108,10 @@ struct GStamp {
     }
 };
 
-template <int BM, int BN, int STAGES, int KG, bool RS, bool PERSIST, int KB>
+// STEP: the launch's one problem ends in the DDPM-step epilogue (gemm_tile.h DdpmEpi) instead of
+// its mode's; the k-loop is the same code, so an element's sum is the one the STEP = false
+// kernel of the same tile forms.
+template <int BM, int BN, int STAGES, int KG, bool RS, bool PERSIST, int KB, bool STEP>
 __global__ __launch_bounds__(256 * KG) void gemm_bf16_kernel(GemmKArgs a) {
     GStamp gs;
     gs.on = GEMM_STAMP && !PERSIST && !RS && blockIdx.x == 0 && threadIdx.x == 0;
@@ -263,6 +267,15 @@ __global__ __launch_bounds__(256 * KG) void gemm_bf16_kernel(GemmKArgs a) {
     auto epi = [&](const TileLoc& L, const f32x16& c, const int i, const int j)
                    __attribute__((always_inline)) {
         KProb& P = ka->prob[L.p];
+        if constexpr (STEP) {
+            const __attribute__((address_space(4))) DdpmEpi& S = ka->step;
+            const int t = S.t;
+            epi_ddpm_block(c, L.m0 + wr * (BM / 2) + i * 32,
+                           L.n0 + wc * (BN / 2) + j * 32 + r32, h, P.M_valid, P.M, P.N, P.bias,
+                           S.x_in, S.z, S.x_out, S.xb, S.ld, S.ldb, S.c1[t], S.c2[t], S.sg[t],
+                           t > 0);
+            return;
+        }
         int mode = P.mode, Mv = P.M_valid, Mr = P.M, Nc = P.N, ksp = ka->ksplit[L.p];
         int kt = P.ct_blk;
         float scale = P.scale;
@@ -635,11 +648,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(ldm_gemm_prob_t P, i
 }
 
 template <int BM, int BN, int STAGES, int KG = 1, bool RS = false, bool PERSIST = false,
-          int KB = 64>
-int launch_gemm(const ldm_gemm_args_t& a, hipStream_t s) {
-    auto* k = &gemm_bf16_kernel<BM, BN, STAGES, KG, RS, PERSIST, KB>;
+          int KB = 64, bool STEP = false>
+int launch_gemm(const ldm_gemm_args_t& a, hipStream_t s, const DdpmEpi* step = nullptr) {
+    auto* k = &gemm_bf16_kernel<BM, BN, STAGES, KG, RS, PERSIST, KB, STEP>;
     GemmKArgs ka;
     memset(&ka, 0, sizeof(ka));
+    if (STEP) ka.step = *step;
     ka.n_prob = a.n_prob;
     int acc = 0;
     for (int p = 0; p < LDM_GEMM_MAX_PROBS; ++p) {
@@ -842,6 +856,24 @@ int gemm_bf16(const ldm_gemm_args_t& a, hipStream_t s) {
         default: break;
     }
     set_error("ldm_gemm_bf16: tile %d", tile);
+    return LDM_EINVAL;
+}
+
+// The out-projection of ldm_sample_batch (sample_batch.hip): one problem, one segment, no
+// split-K, on the caller's tile (4 or 24: the two ldm_sample_batch runs on), ending in the
+// DDPM-step epilogue.  Internal: the problem's own mode and outputs are ignored, and the caller
+// has checked operands, strides and extents (it built them).
+int gemm_bf16_ddpm(const ldm_gemm_args_t& a, const gtile::DdpmEpi& e, hipStream_t s) {
+    LDM_REQUIRE(a.n_prob == 1 && a.prob[0].n_seg == 1 && a.prob[0].k_split <= 1 &&
+                    a.prob[0].seg[0].K % (a.tile == 24 ? 2 * kBK : kBK) == 0,
+                LDM_EINVAL, "gemm_bf16_ddpm: one problem of one segment, K a multiple of the "
+                "tile's k-step");
+    switch (a.tile) {
+        case 4: return launch_gemm<64, 64, 3, 1, false, false, 64, true>(a, s, &e);
+        case 24: return launch_gemm<64, 64, 4, 2, false, false, 128, true>(a, s, &e);
+        default: break;
+    }
+    set_error("gemm_bf16_ddpm: tile %d", a.tile);
     return LDM_EINVAL;
 }
 

@@ -127,6 +127,56 @@ struct EpiArgs {
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
+// ---- DDPM-step epilogue (internal: the out-projection of ldm_sample_batch) -------------------
+// With pre = acc + bias = eps_hat:  x_out[m][n] = ddpm_update(x_in[m][n], pre, z[m][n], c1[t],
+// c2[t], sigma[t], t > 0) -- the device function ddpm_step_kernel and the GEMV SE_STEP epilogue
+// call, so the update is bitwise the same function of its inputs -- and xb[m][n] = bf16(x_out),
+// the next step's in-projection operand (rows M_valid <= m < M: zeros).  The tables are read on
+// the device at t; z is not read at t == 0.  Not part of ldm_gemm_prob_t: it rides in the
+// launch's internal argument block (gemm_bf16.hip GemmKArgs) and only the kernels instantiated
+// with STEP see it, so ldm_gemm_bf16 through the public ABI has no such mode.
+struct DdpmEpi {
+    const float* x_in;       // fp32 [M_valid][ld]
+    const float* z;          // fp32 [M_valid][ld] (unused at t == 0)
+    float* x_out;            // fp32 [M_valid][ld]
+    unsigned short* xb;      // bf16 [M][ldb]
+    const float* c1;         // schedule tables, device, length > t
+    const float* c2;
+    const float* sg;
+    int64_t ld, ldb;
+    int t, reserved;
+};
+
+// One 32 x 32 accumulator block in accumulator layout: lane = column n, 16 rows (row(v)); the 32
+// lanes of a half-wave cover 128 contiguous bytes of a row per store.
+__device__ __forceinline__ void epi_ddpm_block(const f32x16& c, int rb, int n, int h, int Mv,
+                                               int Mr, int Nc, const float* bias_p,
+                                               const float* x_in, const float* z, float* x_out,
+                                               unsigned short* xb, int64_t ld, int64_t ldb,
+                                               float c1, float c2, float sg, bool add_noise) {
+    const bool ncol = n < Nc;
+    const int nn = ncol ? n : Nc - 1;
+    const float bias = bias_p ? bias_p[nn] : 0.f;
+    auto row = [&](int v) { return rb + (v & 3) + 8 * (v >> 2) + 4 * h; };
+    float xv[16], zv[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {        // padding rows read row 0 (valid) and drop it
+        const int b = row(v);
+        const int64_t at = (int64_t)((ncol && b < Mv) ? b : 0) * ld + nn;
+        xv[v] = x_in[at];
+        zv[v] = add_noise ? z[at] : 0.f;
+    }
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const int b = row(v);
+        const bool live = ncol && b < Mv;
+        const float o = ddpm_update(xv[v], c[v] + bias, zv[v], c1, c2, sg, add_noise);
+        if (live) x_out[(int64_t)b * ld + n] = o;
+        if (ncol && b < Mr)
+            xb[(int64_t)b * ldb + n] = (unsigned short)(pack2_bf16(live ? o : 0.f, 0.f) & 0xffffu);
+    }
+}
+
 // ---- LDS-transposed epilogue of one 32 x 32 accumulator block ------------------------------
 // The accumulator layout gives a lane ONE column of 16 rows, so the row-major outputs would take
 // one 4-byte (bf16: 2-byte) store per element: 16-52 store instructions per 32 x 32 block, and a

@@ -156,7 +156,8 @@ class Sampler:
 
     def __init__(self, denoiser, schedule: DDPMSchedule, n: int, *,
                  steps: Optional[int] = None, dtype: str = "bf16", device=None,
-                 use_graph: bool = True, persistent: Optional[bool] = None):
+                 use_graph: bool = True, persistent: Optional[bool] = None,
+                 batched: Optional[bool] = None):
         self.device = torch.device(device or torch.device("cuda", torch.cuda.current_device()))
         self.model, self.schedule, self.n = denoiser, schedule, n
         self.T = schedule.T
@@ -170,16 +171,34 @@ class Sampler:
         self.x2 = torch.empty(2, n, D, device=self.device)
         self.x = [self.x2[0], self.x2[1]]
         self.noise = torch.empty(self.T, n, D, device=self.device)
-        self.step = denoiser.make_stepper(n, dtype, self.device, self.sd["desc"])
         self.graph = None
         self.use_graph = use_graph
+        self.loop = None
+        self.loop_fallbacks = 0
+        # batched=None (default): a denoiser whose per-step / persistent kernels stop at a batch
+        # cap (the MLP: SMALL_MAX_BATCH = 16) runs larger batches through its matrix-core loop
+        # (ldm_sample_batch): one C call enqueues the whole loop, and use_graph
+        # captures that call once (a linear chain of kernel nodes) and replays it.  True: that
+        # loop at any n.  It is bf16 only and has no per-step form.
+        small = getattr(denoiser, "SMALL_MAX_BATCH", None)
+        self.batched = bool(batched) if batched is not None else (small is not None and n > small)
+        if self.batched:
+            if small is None:
+                raise capi.LdmError(f"{type(denoiser).__name__} has no batched sampling loop")
+            if dtype != "bf16" or persistent is False:
+                raise capi.LdmError(
+                    f"Sampler: n = {n} latents per call runs the bf16 matrix-core loop only "
+                    f"(got dtype={dtype!r}, persistent={persistent!r}); the fp32 and per-step "
+                    f"kernels take at most {small} (sample(form='loop16') groups a batch so)")
+            self.step = None
+            self.loop = denoiser.make_loop(n, dtype, self.device, self.sd["desc"], batched=True)
+            return
+        self.step = denoiser.make_stepper(n, dtype, self.device, self.sd["desc"])
         # persistent=None (default): the whole loop as one persistent launch (ldm_sample_loop,
         # bit-identical, +10-13 % on MI355X: DESIGN.md §5) whenever the denoiser has a kernel
         # for this shape, else per-step launches; True: require it; False: per-step launches,
         # graph-replayed when use_graph.
         make_loop = getattr(denoiser, "make_loop", None)
-        self.loop = None
-        self.loop_fallbacks = 0
         # a denoiser whose loop does not beat its per-step graph at this batch (prefer_loop(n)
         # False) runs the graph unless the loop is asked for; the 1D-UNet has no loop (its
         # one-launch loop was retired in round 4 at 0.53x the graph)
@@ -219,13 +238,28 @@ class Sampler:
             # weights / E tables (descriptors are updated in place) and re-capture the graph,
             # which baked the old table addresses in
             self.model.device_pack(self.dtype, self.device)
-            self.step = self.model.make_stepper(self.n, self.dtype, self.device, self.sd["desc"])
-            if self.loop is not None:
-                self.loop = self.model.make_loop(self.n, self.dtype, self.device, self.sd["desc"])
+            if self.batched:
+                self.loop = self.model.make_loop(self.n, self.dtype, self.device,
+                                                 self.sd["desc"], batched=True)
+            else:
+                self.step = self.model.make_stepper(self.n, self.dtype, self.device,
+                                                    self.sd["desc"])
+                if self.loop is not None:
+                    self.loop = self.model.make_loop(self.n, self.dtype, self.device,
+                                                     self.sd["desc"])
             self.graph = None
             self._gen = gen
         self.x[0].copy_(x_T)
         self.noise[:noise.shape[0]].copy_(noise)
+        if self.batched:
+            run = lambda: self.loop(self.x2, self.noise, self.T - 1, self.steps)   # noqa: E731
+            if not self.use_graph:
+                run()
+                return self.result
+            if self.graph is None:
+                self.graph = self._capture(run, x_T)
+            self.graph.replay()
+            return self.result
         if self.loop is not None:
             self.loop(self.x2, self.noise, self.T - 1, self.steps)
             if not check:
@@ -249,44 +283,117 @@ class Sampler:
             self._loop()
             return self.result
         if self.graph is None:
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):
-                self._loop()          # warm-up (module load, first-launch costs)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            self.x[0].copy_(x_T)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._loop()
-            self.graph = g
+            self.graph = self._capture(self._loop, x_T)
         self.graph.replay()
         return self.result
+
+    def _capture(self, run, x_T: torch.Tensor):
+        s = torch.cuda.Stream(self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            run()                     # warm-up (module load, first-launch costs)
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        self.x[0].copy_(x_T)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            run()
+        return g
+
+
+# The smallest batch from which sample(form="auto") runs the matrix-core loop ("batched") rather
+# than groups of <= 16 through the persistent GEMV loop ("loop16"): the measured crossover of
+# scripts/bench_sample_batch.py (profiles/sample_batch/bench.json): on the MI355X
+# "batched" runs at 0.58x / 0.73x of "loop16" at n = 17 / 32 and at 1.43x / 2.8x / 5.6x / 20.8x at
+# n = 64 / 128 / 256 / 1024 (its time per step hardly moves up to one 1024-row group, while
+# "loop16" runs its groups one after the other).  Between 32 and 64 nothing was measured.
+BATCHED_FROM = 64
+SAMPLE_FORMS = ("auto", "loop16", "batched")
+SAMPLE_CHUNK = 1024          # rows per "batched" group: bounds the [T, chunk, D] noise (1 GB)
+SMALL_GROUP = 16             # rows per "loop16" group: the GEMV kernels' batch cap
+
+
+def sample_groups(n: int, form: str = "auto", chunk: Optional[int] = None,
+                  batched_from: Optional[int] = None) -> Tuple[str, List[Tuple[int, int]]]:
+    """How ``sample`` runs ``n`` rows: ``(kind, [(lo, hi), ...])``, the row ranges in order.
+
+    kind "single": one call on today's <= 16 path (``form="auto"``, n <= 16);
+    "loop16": groups of <= 16 rows, each through that same path;
+    "batched": groups of at most ``chunk`` rows (default ``SAMPLE_CHUNK``), each through the
+    matrix-core loop -- also a tail group of <= 16 rows, so every row sees one arithmetic.
+    ``form="auto"`` picks "loop16" below ``batched_from`` (default ``BATCHED_FROM``) and
+    "batched" from there on.  A pure function of its arguments."""
+    if form not in SAMPLE_FORMS:
+        raise ValueError(f"form must be one of {SAMPLE_FORMS}, got {form!r}")
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError("chunk must be >= 1")
+    if form == "auto":
+        if n <= SMALL_GROUP:
+            return "single", [(0, n)]
+        form = "loop16" if n < (BATCHED_FROM if batched_from is None else batched_from) \
+            else "batched"
+    size = SMALL_GROUP if form == "loop16" else int(chunk or SAMPLE_CHUNK)
+    return form, [(lo, min(lo + size, n)) for lo in range(0, n, size)]
 
 
 def sample(denoiser, schedule: DDPMSchedule, n: int, *,
            steps: Optional[int] = None, dtype: str = "bf16", x_T: Optional[torch.Tensor] = None,
            noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
            device=None, use_graph: bool = True, persistent: Optional[bool] = None,
-           group=None) -> torch.Tensor:
+           group=None, form: str = "auto", chunk: Optional[int] = None) -> torch.Tensor:
     """DDPM ancestral sampling (DDPM Alg. 2) of ``n`` latent codes.
 
     ``x_T [n, D]`` and ``noise [T, n, D]`` may be given (parity mode: the same numbers the
     CPU oracle consumes); otherwise they are drawn on the device.  With a process group the
     batch is sharded over ranks and the latents all-gathered.
+
+    ``form`` (MLP denoiser; ``sample_groups``): "auto" keeps the single call for n <= 16, runs
+    groups of <= 16 through the persistent loop ("loop16") below ``BATCHED_FROM`` and the
+    matrix-core loop ("batched", bf16, groups of at most ``chunk`` rows) from there on.  The
+    two are different arithmetic (fp32 against bf16 activations), so pass the
+    form where runs at different n must agree bit for bit; within a form a row's result does not
+    depend on n or chunk.  Device RNG order for n > 16: ``x_T [n, D]`` first, then one
+    ``[T, c, D]`` noise draw per group of c rows, in group order; a caller's
+    ``noise [T, n, D]`` is cut into the groups' column slices.  A denoiser without a batch
+    cap (the 1D-UNet) ignores ``form`` and runs one call.
     """
+    if form not in SAMPLE_FORMS:
+        raise ValueError(f"form must be one of {SAMPLE_FORMS}, got {form!r}")
     device = torch.device(device or torch.device("cuda", torch.cuda.current_device()))
     world, rank = ldist.world_and_rank(group)
     lo, hi = ldist.batch_shard(n, rank, world)
     nl = hi - lo
     D, T = denoiser.D, schedule.T
+    if getattr(denoiser, "SMALL_MAX_BATCH", None) is None:
+        kind, groups = "single", [(0, nl)]
+    else:
+        kind, groups = sample_groups(nl, form, chunk)
     if x_T is None:
         x_T = torch.randn(n, D, device=device, generator=generator)
-    if noise is None:
-        noise = torch.randn(T, n, D, device=device, generator=generator)
     x_T = x_T.to(device, torch.float32)[lo:hi].contiguous()
-    noise = noise.to(device, torch.float32)[:, lo:hi].contiguous()
-    out = Sampler(denoiser, schedule, nl, steps=steps, dtype=dtype, device=device,
-                  use_graph=use_graph, persistent=persistent).run(x_T, noise).clone()
+    if kind == "single":
+        if noise is None:
+            noise = torch.randn(T, n, D, device=device, generator=generator)
+        noise = noise.to(device, torch.float32)[:, lo:hi].contiguous()
+        out = Sampler(denoiser, schedule, nl, steps=steps, dtype=dtype, device=device,
+                      use_graph=use_graph, persistent=persistent).run(x_T, noise).clone()
+        return ldist.all_gather_rows(out, n, group=group)
+    out = torch.empty(nl, D, device=device)
+    samplers: Dict[int, Sampler] = {}            # one per group size (at most two)
+    for g0, g1 in groups:
+        c = g1 - g0
+        if noise is None:
+            z = torch.randn(T, c, D, device=device, generator=generator)
+        else:
+            z = noise[:, lo + g0:lo + g1].to(device, torch.float32).contiguous()
+        if c not in samplers:
+            samplers[c] = Sampler(denoiser, schedule, c, steps=steps, dtype=dtype, device=device,
+                                  use_graph=use_graph, persistent=persistent,
+                                  batched=kind == "batched")
+        out[g0:g1] = samplers[c].run(x_T[g0:g1], z)
+        del z
     return ldist.all_gather_rows(out, n, group=group)
 
 

@@ -349,11 +349,20 @@ class MLPDenoiser:
         step.keep = keep
         return step
 
-    def make_loop(self, n: int, dtype: str, device, sched_desc):
+    def make_loop(self, n: int, dtype: str, device, sched_desc, batched: Optional[bool] = None):
         """Callable ``loop(x2, noise, t_hi, steps)`` running the whole reverse loop as one
         persistent launch (``ldm_sample_loop``), or None when the shape has no persistent
-        kernel (the per-step stepper is used then)."""
+        kernel (the per-step stepper is used then).
+
+        ``n > SMALL_MAX_BATCH`` (16, the GEMV kernels' cap): the matrix-core loop
+        (``ldm_sample_batch``, bf16 only) behind the same callable, with ``batched = True`` and
+        a ``status()`` that is always 0 (it has no grid barrier to give up on).  There is no
+        other kernel for such a batch, so an unsupported shape raises ``LdmError``.
+        ``batched=True`` asks for that loop at any n (the tail group of a chunked batch, which
+        must run the same arithmetic as the groups before it)."""
         from . import ops
+        if batched or (batched is None and n > self.SMALL_MAX_BATCH):
+            return self._make_batched_loop(n, dtype, device, sched_desc)
         desc, keep, gen = self._pinned_pack(dtype, device)
         if not ops.sample_loop_supported(desc, n):
             return None
@@ -369,6 +378,30 @@ class MLPDenoiser:
         # status 2 (replica placement mismatch) switches this device to the chip-wide loop
         # inside the library, so the Sampler keeps launching the loop
         loop.placement_fallback = True
+        return loop
+
+    SMALL_MAX_BATCH = 16      # the per-step / persistent GEMV kernels' batch cap (csrc kSmallMaxB)
+
+    def _make_batched_loop(self, n: int, dtype: str, device, sched_desc):
+        from . import ops
+        if dtype != "bf16":
+            raise capi.LdmError(f"the batched sampling loop (n = {n}; every batch above "
+                                f"{self.SMALL_MAX_BATCH}) runs bf16 weights only (got "
+                                f"dtype={dtype!r}); sample fp32 in groups of <= "
+                                f"{self.SMALL_MAX_BATCH}")
+        desc, keep, gen = self._pinned_pack(dtype, device)
+        if not ops.sample_batch_supported(desc, n):
+            raise capi.LdmError("no batched sampling kernel for this denoiser / batch: "
+                                + capi.load().ldm_last_error().decode(errors="replace"))
+        ws = ops.sample_batch_workspace(desc, n, device)
+
+        def loop(x2, noise, t_hi, steps):
+            self._check_gen(gen, "sampling loop")
+            ops.sample_batch(desc, sched_desc, x2, noise, t_hi, steps, ws)
+            return ws
+        loop.keep = keep
+        loop.status = lambda: 0
+        loop.batched = True
         return loop
 
     def device_pack(self, dtype: str, device, with_tables: bool = True) -> Dict[str, object]:

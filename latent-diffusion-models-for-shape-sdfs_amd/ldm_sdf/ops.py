@@ -394,6 +394,41 @@ def sample_loop_status(desc: capi.Denoiser, ws: torch.Tensor, B: int) -> int:
     return int(st.value)
 
 
+def sample_batch_supported(desc: capi.Denoiser, B: int) -> bool:
+    return bool(capi.load().ldm_sample_batch_supported(C.byref(desc), int(B)))
+
+
+def sample_batch_workspace(desc: capi.Denoiser, B: int, device) -> torch.Tensor:
+    """The workspace of ``sample_batch`` for batch B: uint8, 256-byte aligned."""
+    n = int(capi.load().ldm_sample_batch_ws_bytes(C.byref(desc), int(B)))
+    if n == 0:
+        raise capi.LdmError("ldm_sample_batch_ws_bytes: unsupported denoiser shape or batch: "
+                            + capi.load().ldm_last_error().decode(errors="replace"))
+    ws = torch.empty(n + 256, device=device, dtype=torch.uint8)
+    off = (-ws.data_ptr()) % 256
+    return ws[off:off + n]
+
+
+def sample_batch(desc: capi.Denoiser, sched_desc: capi.Sched, x2: torch.Tensor,
+                 noise: torch.Tensor, t_hi: int, steps: int, ws: torch.Tensor) -> None:
+    """A10 for batches above 16 on the matrix cores (``ldm_sample_batch``): ``x2 [2, B, D]``
+    holds x_T in ``x2[0]`` and the result in ``x2[steps & 1]``; ``noise [T, B, D]`` (``noise[t]``
+    is the z of step t; not read at t = 0).  One call enqueues every launch of the loop."""
+    capi.require_device(x2, noise, ws)
+    _contig(x2, noise, ws)
+    if x2.dtype != torch.float32 or noise.dtype != torch.float32 or x2.dim() != 3 or \
+            x2.shape[0] != 2 or x2.shape[2] != desc.D or \
+            noise.dim() != 3 or noise.shape[1:] != x2.shape[1:] or noise.shape[0] <= int(t_hi):
+        raise capi.LdmError(f"sample_batch: x2 must be fp32 [2, B, {desc.D}] and noise fp32 "
+                            f"[> t_hi, B, {desc.D}] (got {tuple(x2.shape)}, {tuple(noise.shape)})")
+    B = x2.shape[1]
+    capi.check(capi.load().ldm_sample_batch(C.byref(desc), C.byref(sched_desc), x2.data_ptr(),
+                                            noise.data_ptr(), int(t_hi), int(steps), B,
+                                            ws.data_ptr(), ws.numel() * ws.element_size(),
+                                            capi.stream_handle(x2.device)),
+               "ldm_sample_batch")
+
+
 LOOP_FORMS = {"auto": 0, "replica": 1, "xcd": 2, "direct": 3, "flat": 4}
 LOOP_FORM_NAMES = {v: k for k, v in LOOP_FORMS.items()}
 
