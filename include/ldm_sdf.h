@@ -828,6 +828,59 @@ int ldm_ray_mesh(const float* verts, int V, const int32_t* faces, int F, const f
 int ldm_ray_mesh_face_chunk(void);
 int64_t ldm_ray_mesh_split_below(void);
 
+/* ---- sphere tracing of the decoder's field (additive in ABI 7) ------------- */
+/* The passes between two decoder evaluations of a sphere tracer; the loop over rounds is the
+ * caller's (ldm_sdf/render.py trace_sdf), and every evaluation is one ldm_decoder_points_fwd
+ * over the whole batch.  B shapes, R rays each: origins / dirs fp32 [R][3] shared by the shapes
+ * (per_shape == 0) or [B][R][3] (per_shape != 0); a direction need not be unit and t is in
+ * units of it.  The geometry is csrc/ray_brick_dda.h in plain fp32, a fixed operation order, no
+ * fused multiply-add: a ray's outputs are a pure function of the ray, its values and the
+ * parameters, bitwise the same alone or in any batch.  State, all caller-owned:
+ *   t        [B][R]     the ray's current t; +inf once it has missed
+ *   status   [B][R]     0 miss, 1 hit (at t), 2 still marching
+ *   steps    [B][R]     decoder evaluations the ray has taken
+ *   xyz_last [B][R][3]  (or NULL) the point the ray was last evaluated at, NaN for none
+ *   list     [B][R]     per shape the first counts[b] entries: the marching rays, ascending
+ *   counts   [B]        the caller reads these back once per round
+ * ldm_sdf_trace_init: a ray with a non-finite origin or a zero or non-finite direction
+ * misses; else it is slab-clipped against [lo, hi]^3 and [t_min, t_max], and it starts at the
+ * near end.  With mask != NULL -- brick flags [B nb^3] for an N^3 grid of voxel size vs over
+ * the box: ldm_band_classify's `active`, to which a caller adds the inactive bricks that lie
+ * inside the shape, where a ray must not be carried on -- it starts at its entry into the first
+ * flagged brick (brick
+ * boundaries: the lattice coordinates of ldm_band_lattice_coords, the thinner last brick
+ * included), or misses.  level, lipschitz, eps and max_steps are only checked here, so that a
+ * march is refused before its first round.
+ * ldm_sdf_trace_emit: xyz [B][P][3] = the points origin + t dir of the listed rays, P >= the
+ * largest count; a shorter shape's remaining slots repeat its last listed point (lo, lo, lo
+ * for a shape with none).
+ * ldm_sdf_trace_step: vals [B][P] the decoder's values at those points.  f = v - level:
+ * f <= eps or f not finite is a hit at the current t; else t += max(f, eps) / (lipschitz |dir|),
+ * with a mask then forward through inactive bricks to the next active one, past the ray's far
+ * end a miss.  list and counts are rewritten for the next round.
+ * LDM_EINVAL for a NULL required pointer, B < 1, R < 1, B R above 2^31 - 1, more than 65535
+ * shapes or chunks of 4096 rays, P outside [1, R], a box that is not finite with lo < hi,
+ * t_min > t_max or a NaN bound, eps or lipschitz not positive and finite, a NaN level,
+ * max_steps < 1, and with a mask N < 2, B nb^3 above 2^31 - 1 or vs not positive; LDM_EALIGN
+ * for tensors off 4 B or a workspace off 256 B; LDM_ENOSPC for a workspace below
+ * ldm_sdf_trace_ws_bytes(B, R) (0 for sizes the calls refuse).  Every refusal happens before
+ * any device work. */
+size_t ldm_sdf_trace_ws_bytes(int B, int64_t R);
+int ldm_sdf_trace_init(const float* origins, const float* dirs, int per_shape, int B, int64_t R,
+                       float lo, float hi, float t_min, float t_max, float level,
+                       float lipschitz, float eps, int max_steps, const uint8_t* mask, int N,
+                       float vs, float* t, int32_t* status, int32_t* steps, float* xyz_last,
+                       int32_t* list, int32_t* counts, void* ws, size_t ws_bytes,
+                       ldm_stream_t s);
+int ldm_sdf_trace_emit(const float* origins, const float* dirs, int per_shape, int B, int64_t R,
+                       int P, float lo, const float* t, const int32_t* list,
+                       const int32_t* counts, float* xyz, ldm_stream_t s);
+int ldm_sdf_trace_step(const float* origins, const float* dirs, int per_shape, int B, int64_t R,
+                       int P, const float* vals, float lo, float level, float lipschitz,
+                       float eps, const uint8_t* mask, int N, float vs, float* t,
+                       int32_t* status, int32_t* steps, float* xyz_last, int32_t* list,
+                       int32_t* counts, void* ws, size_t ws_bytes, ldm_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

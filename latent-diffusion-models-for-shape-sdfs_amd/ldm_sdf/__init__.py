@@ -20,8 +20,8 @@ from .meshsdf import mesh_sdf, normalize_mesh, sample_sdf, sample_surface  # noq
 from .metrics import (chamfer_distance, chamfer_matrix, emd_distance,  # noqa: F401
                       emd_matrix, evaluate_generation, generation_metrics, nearest_points,
                       shape_clouds)
-from .render import (camera_rays, depth_samples, look_at, ray_mesh, read_png,  # noqa: F401
-                     render_mesh, write_png)
+from .render import (camera_rays, depth_samples, estimate_lipschitz, look_at,  # noqa: F401
+                     ray_mesh, read_png, render_mesh, render_sdf, trace_sdf, write_png)
 from . import ops, dist, pack, data, meshsdf, metrics, render  # noqa: F401
 from ._capi import LdmError, load as load_library  # noqa: F401
 

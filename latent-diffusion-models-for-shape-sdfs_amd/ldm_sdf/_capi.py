@@ -260,6 +260,12 @@ SIGNATURES = [
                           _sz, _vp]),
     ("ldm_ray_mesh_face_chunk", _i, []),
     ("ldm_ray_mesh_split_below", C.c_int64, []),
+    ("ldm_sdf_trace_ws_bytes", _sz, [_i, C.c_int64]),
+    ("ldm_sdf_trace_init", _i, [_fp, _fp, _i, _i, C.c_int64, _f, _f, _f, _f, _f, _f, _f, _i, _vp,
+                                _i, _f, _fp, _vp, _vp, _fp, _vp, _vp, _vp, _sz, _vp]),
+    ("ldm_sdf_trace_emit", _i, [_fp, _fp, _i, _i, C.c_int64, _i, _f, _fp, _vp, _vp, _fp, _vp]),
+    ("ldm_sdf_trace_step", _i, [_fp, _fp, _i, _i, C.c_int64, _i, _fp, _f, _f, _f, _f, _vp, _i,
+                                _f, _fp, _vp, _vp, _fp, _vp, _vp, _vp, _sz, _vp]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -1186,3 +1186,87 @@ def ray_mesh(verts: torch.Tensor, faces: torch.Tensor, origins: torch.Tensor,
                                         capi.ptr(bary), capi.ptr(flag), capi.ptr(ws), ws.numel(),
                                         capi.stream_handle(dev)), "ldm_ray_mesh")
     return t, face, bary, flag
+
+
+# ------------------------------------------------------------------ sphere tracing
+class SdfTraceState:
+    """The device buffers of one march (``ldm_sdf_trace_*``): ``t``, ``status``, ``steps``
+    ``[B, R]``, ``xyz_last [B, R, 3]`` or None, ``list [B, R]`` int32 (per shape the first
+    ``counts[b]`` entries: the marching rays, ascending), ``counts [B]`` int32, and the rays,
+    box, march parameters and brick mask the three calls share."""
+
+    def __init__(self, origins: torch.Tensor, dirs: torch.Tensor, B: int, bbox, level: float,
+                 lipschitz: float, eps: float, mask: Optional[torch.Tensor], N: int,
+                 want_points: bool):
+        capi.require_device(origins, dirs, mask)
+        _contig(origins, dirs, mask)
+        _f32(origins, dirs)
+        if origins.shape != dirs.shape or origins.dim() not in (2, 3) or origins.shape[-1] != 3:
+            raise capi.LdmError("sdf_trace: origins and dirs must both be [R, 3] or [B, R, 3]")
+        self.per_shape = int(origins.dim() == 3)
+        if self.per_shape and origins.shape[0] != B:
+            raise capi.LdmError(f"sdf_trace: per-shape rays must be [B = {B}, R, 3]")
+        self.B, self.R = int(B), int(origins.shape[-2])
+        self.origins, self.dirs = origins, dirs
+        self.lo, self.hi = float(bbox[0]), float(bbox[1])
+        self.level, self.lipschitz, self.eps = float(level), float(lipschitz), float(eps)
+        self.mask, self.N = mask, int(N)
+        self.vs = voxel_size(self.N, bbox) if mask is not None else 0.0
+        if mask is not None and (mask.dtype != torch.uint8 or
+                                 mask.numel() != self.B * _nb(self.N) ** 3):
+            raise capi.LdmError("sdf_trace: mask must be uint8 [B * nb^3] (band_classify's active)")
+        dev = self.dev = origins.device
+        n = (self.B, self.R)
+        self.t = torch.empty(n, device=dev, dtype=torch.float32)
+        self.status = torch.empty(n, device=dev, dtype=torch.int32)
+        self.steps = torch.empty(n, device=dev, dtype=torch.int32)
+        self.xyz_last = torch.empty(n + (3,), device=dev, dtype=torch.float32) \
+            if want_points else None
+        self.list = torch.empty(n, device=dev, dtype=torch.int32)
+        self.counts = torch.empty(self.B, device=dev, dtype=torch.int32)
+        need = capi.load().ldm_sdf_trace_ws_bytes(self.B, self.R) if self.R > 0 else 0
+        if self.R > 0 and need == 0:
+            raise capi.LdmError(f"sdf_trace: B * R = {self.B} * {self.R} does not fit 31 bits")
+        self.ws = torch.empty(max(need, 256), device=dev, dtype=torch.uint8)
+
+
+def sdf_trace_init(st: SdfTraceState, t_min: float, t_max: float, max_steps: int) -> None:
+    """``ldm_sdf_trace_init``: clip, first active brick, the first list and counts."""
+    with torch.cuda.device(st.dev):
+        capi.check(capi.load().ldm_sdf_trace_init(
+            capi.ptr(st.origins), capi.ptr(st.dirs), st.per_shape, st.B, st.R, st.lo, st.hi,
+            float(t_min), float(t_max), st.level, st.lipschitz, st.eps, int(max_steps),
+            capi.ptr(st.mask), st.N, st.vs, capi.ptr(st.t), capi.ptr(st.status),
+            capi.ptr(st.steps), capi.ptr(st.xyz_last), capi.ptr(st.list), capi.ptr(st.counts),
+            capi.ptr(st.ws), st.ws.numel(), capi.stream_handle(st.dev)), "ldm_sdf_trace_init")
+
+
+def sdf_trace_emit(st: SdfTraceState, P: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``ldm_sdf_trace_emit``: the listed rays' points as ``[B, P, 3]``."""
+    if out is None:
+        out = torch.empty(st.B, int(P), 3, device=st.dev, dtype=torch.float32)
+    if out.shape != (st.B, int(P), 3) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise capi.LdmError("sdf_trace_emit: out must be a contiguous float32 [B, P, 3]")
+    with torch.cuda.device(st.dev):
+        capi.check(capi.load().ldm_sdf_trace_emit(
+            capi.ptr(st.origins), capi.ptr(st.dirs), st.per_shape, st.B, st.R, int(P), st.lo,
+            capi.ptr(st.t), capi.ptr(st.list), capi.ptr(st.counts), capi.ptr(out),
+            capi.stream_handle(st.dev)), "ldm_sdf_trace_emit")
+    return out
+
+
+def sdf_trace_step(st: SdfTraceState, vals: torch.Tensor) -> None:
+    """``ldm_sdf_trace_step`` on the decoder's values ``[B, P]`` at the emitted points; the
+    list and the counts are rewritten for the next round."""
+    capi.require_device(vals)
+    _f32(vals)
+    _contig(vals)
+    if vals.dim() != 2 or vals.shape[0] != st.B:
+        raise capi.LdmError("sdf_trace_step: vals must be [B, P]")
+    with torch.cuda.device(st.dev):
+        capi.check(capi.load().ldm_sdf_trace_step(
+            capi.ptr(st.origins), capi.ptr(st.dirs), st.per_shape, st.B, st.R,
+            int(vals.shape[1]), capi.ptr(vals), st.lo, st.level, st.lipschitz, st.eps,
+            capi.ptr(st.mask), st.N, st.vs, capi.ptr(st.t), capi.ptr(st.status),
+            capi.ptr(st.steps), capi.ptr(st.xyz_last), capi.ptr(st.list), capi.ptr(st.counts),
+            capi.ptr(st.ws), st.ws.numel(), capi.stream_handle(st.dev)), "ldm_sdf_trace_step")

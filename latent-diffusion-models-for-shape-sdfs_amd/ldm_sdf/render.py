@@ -26,7 +26,8 @@ from . import ops
 from .meshsdf import _check_indices, _check_mesh
 
 __all__ = ["ray_mesh", "look_at", "camera_rays", "render_mesh", "write_png", "read_png",
-           "depth_samples", "face_chunk", "split_below"]
+           "depth_samples", "face_chunk", "split_below", "trace_sdf", "render_sdf",
+           "estimate_lipschitz", "skip_mask"]
 
 
 def face_chunk() -> int:
@@ -209,6 +210,166 @@ def depth_samples(origins: torch.Tensor, dirs: torch.Tensor, t: torch.Tensor,
     sdf = torch.cat([torch.full((M,), eta, dtype=p.dtype, device=p.device),
                      torch.full((M,), -eta, dtype=p.dtype, device=p.device)])
     return xyz, sdf
+
+
+# ------------------------------------------------------- sphere tracing
+def _shade(mask, n, d, background):
+    """``render_mesh``'s headlight Lambert image from facing unit normals (any leading shape)."""
+    lam = torch.where(mask, (n * d).sum(-1).abs(),
+                      torch.full(mask.shape, float(background), device=n.device))
+    grey = (lam * 255.0 + 0.5).floor().clamp(0, 255).to(torch.uint8)
+    return grey[..., None].expand(*grey.shape, 3).contiguous()
+
+
+def skip_mask(desc, beta: torch.Tensor, N: int, bbox, level: float, lipschitz: float,
+              eps: float) -> torch.Tensor:
+    """The brick flags ``[B nb^3]`` (uint8) that ``trace_sdf`` skips by, for an ``N^3`` grid:
+    ``decode_band``'s sequence (lattice coordinates, the decoder on them, ``band_classify``) with
+    ``band = lipschitz 4 sqrt(3) voxel_size + eps``, and on top of its ``active`` flags every
+    inactive brick that lies INSIDE the shape (corner-0 value <= level; all corners of an
+    inactive brick are on one side).  A ray may only pass through bricks that are wholly
+    outside: in a brick inside the shape its next evaluation is a hit, as without a mask."""
+    B, nb = beta.shape[0], ops._nb(N)
+    band = float(lipschitz) * 4.0 * math.sqrt(3.0) * ops.voxel_size(N, bbox) + float(eps)
+    lat = ops.band_lattice_coords(N, bbox, device=beta.device)[None].expand(B, -1, -1).contiguous()
+    coarse = ops.decoder_points_fwd(desc, beta, lat)
+    active, _, _ = ops.band_classify(coarse, N, level, band)
+    inside = coarse.view(B, nb + 1, nb + 1, nb + 1)[:, :nb, :nb, :nb] <= float(level)
+    return torch.where(inside.reshape(-1), torch.ones_like(active), active).contiguous()
+
+
+def trace_sdf(decoder, latents: torch.Tensor, origins: torch.Tensor, dirs: torch.Tensor, *,
+              bbox: Tuple[float, float] = (-1.0, 1.0), level: float = 0.0,
+              lipschitz: float = 1.0, eps: float = 1e-3, max_steps: int = 256,
+              t_min: float = 0.0, t_max: float = math.inf, dtype: str = "auto",
+              skip_resolution: Optional[int] = None, return_points: bool = False):
+    """Sphere tracing of the decoded field of ``latents [B, L]``: the rays ``origins + t dirs``
+    (``[R, 3]`` shared by the shapes, or ``[B, R, 3]``; fp32, ``dirs`` need not be unit and
+    ``t`` is in units of it, as in ``ray_mesh``) marched inside ``bbox^3`` and ``[t_min, t_max]``
+    to the first point with ``f = sdf - level <= eps``.
+
+    A ray steps by ``max(f, eps) / (lipschitz |d|)``: it cannot pass through the surface of a
+    field that changes by at most ``lipschitz`` per unit length.  A trained DeepSDF is not an
+    exact distance; ``lipschitz`` is the caller's knob (``estimate_lipschitz`` measures a
+    starting value), and a value below the field's true slope can step over thin parts.
+
+    Returns ``t [B, R]`` (``+inf`` unless the ray hit), ``status [B, R]`` int32 (0 miss, 1 hit,
+    2 still marching after ``max_steps`` evaluations), ``steps [B, R]`` int32 (decoder
+    evaluations of the ray), and with ``return_points`` the point ``[B, R, 3]`` each ray was
+    last evaluated at (NaN for a ray that never was).  A ray with a non-finite origin or a zero
+    or non-finite direction misses.
+
+    ``skip_resolution=N`` classifies the 8^3-voxel bricks of an ``N^3`` grid as ``decode_band``
+    does (band ``lipschitz 4 sqrt(3) voxel_size + eps``) and moves every ray through the bricks
+    that lie wholly OUTSIDE the shape without evaluating the decoder there (``skip_mask``); its
+    soundness is ``decode_band``'s.  Bricks wholly inside the shape are not passed through: a
+    ray that starts inside the shape hits at its first point, as without skipping.
+
+    Each round is one decoder launch over all shapes (``decode_points``'s kernel, ``dtype`` as
+    in ``decode``) and one read of ``B`` counts back to the host.  A ray's outputs are bitwise
+    the same alone, in any batch and in any order of the rays."""
+    from .api import resolve_decode_dtype
+    capi.require_device(latents, origins, dirs)
+    if latents.dim() == 1:
+        latents = latents[None]
+    if latents.dim() != 2 or latents.shape[1] != decoder.latent_dim:
+        raise ValueError(f"latents must be [B, {decoder.latent_dim}]")
+    B = latents.shape[0]
+    if origins.shape != dirs.shape or origins.dim() not in (2, 3) or origins.shape[-1] != 3 \
+            or (origins.dim() == 3 and origins.shape[0] != B):
+        raise ValueError("trace_sdf: origins and dirs must both be [R, 3] or [B, R, 3]")
+    lo, hi = float(bbox[0]), float(bbox[1])
+    level, lipschitz, eps = float(level), float(lipschitz), float(eps)
+    t_min, t_max, max_steps = float(t_min), float(t_max), int(max_steps)
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+        raise ValueError("trace_sdf: bbox must be finite with lo < hi")
+    if not (eps > 0.0 and math.isfinite(eps)) or not (lipschitz > 0.0 and math.isfinite(lipschitz)):
+        raise ValueError("trace_sdf: eps and lipschitz must be positive and finite")
+    if max_steps < 1 or not t_min <= t_max or math.isnan(level):
+        raise ValueError("trace_sdf: need max_steps >= 1, t_min <= t_max and a level")
+    if skip_resolution is not None and int(skip_resolution) < 2:
+        raise ValueError("trace_sdf: skip_resolution must be >= 2")
+    dev = latents.device
+    if origins.device != dev or dirs.device != dev:
+        raise capi.LdmError("trace_sdf: latents, origins and dirs must share a device")
+    dtype = resolve_decode_dtype(dtype, latents)
+    desc = decoder.device_pack(dtype, dev)["desc"]
+    beta = ops.decoder_fold(desc, latents.float().contiguous())
+    mask, N = None, 0
+    if skip_resolution is not None:
+        N = int(skip_resolution)
+        mask = skip_mask(desc, beta, N, bbox, level, lipschitz, eps)
+    st = ops.SdfTraceState(origins.float().contiguous(), dirs.float().contiguous(), B, bbox,
+                           level, lipschitz, eps, mask, N, return_points)
+    if st.R > 0:
+        ops.sdf_trace_init(st, t_min, t_max, max_steps)
+        pts = vals = dws = None
+        for _ in range(max_steps):
+            P = max(st.counts.tolist())              # the round's one synchronisation
+            if P == 0:
+                break
+            if pts is None:                          # the counts only fall: sized once
+                pts = torch.empty(B * P * 3, device=dev)
+                vals = torch.empty(B * P, device=dev)
+                dws = torch.empty(max(capi.load().ldm_workspace_bytes_layout(
+                    capi.LDM_OP_DECODER_POINTS, B, P, desc.dtype, desc.layout), 16),
+                    device=dev, dtype=torch.uint8)
+            xyz = ops.sdf_trace_emit(st, P, pts[:B * P * 3].view(B, P, 3))
+            ops.sdf_trace_step(st, ops.decoder_points_fwd(desc, beta, xyz,
+                                                          vals[:B * P].view(B, P), dws))
+    t = torch.where(st.status == 1, st.t, torch.full_like(st.t, math.inf))
+    out = (t, st.status, st.steps)
+    return out + (st.xyz_last,) if return_points else out
+
+
+def render_sdf(decoder, latents: torch.Tensor, pose, fov_y_deg: float, height: int, width: int,
+               *, background: float = 1.0, **trace_kw) -> Dict[str, torch.Tensor]:
+    """Images of the decoded shapes ``latents [B, L]`` from one pinhole camera, without a
+    mesh: ``trace_sdf`` on the camera's rays (``trace_kw`` are its keyword arguments).  The
+    dict has ``render_mesh``'s entries except ``face``, batched: ``t``, ``mask``, ``depth``
+    ``[B, H, W]``, ``normal [B, H, W, 3]`` -- the field's gradient at the hit points
+    (``sdf_grad``, fp16), normalised and flipped to face the camera, zero off the shape --
+    ``image [B, H, W, 3]`` uint8 with the same headlight Lambert shading, and ``origins``,
+    ``dirs [H W, 3]``.  ``t[b]`` and ``normal[b]`` go into ``depth_samples`` unchanged."""
+    from .grad import sdf_grad
+    capi.require_device(latents)
+    if latents.dim() == 1:
+        latents = latents[None]
+    dev = latents.device
+    p = _pose64(pose)
+    o, d = camera_rays(p, fov_y_deg, height, width, device=dev)
+    trace_kw.pop("return_points", None)
+    t, status, _, xyz = trace_sdf(decoder, latents, o, d, return_points=True, **trace_kw)
+    mask = status == 1
+    B, H, W = latents.shape[0], int(height), int(width)
+    pts = torch.where(mask[..., None], xyz, torch.zeros_like(xyz))
+    _, g = sdf_grad(decoder, latents, pts)
+    n = torch.where(mask[..., None], _facing(g, d[None]), torch.zeros_like(g))
+    fwd = torch.tensor((-p[:3, 2]).astype(np.float32), device=dev)
+    depth = torch.where(mask, t * (d * fwd).sum(-1)[None], torch.full_like(t, math.inf))
+    return {"t": t.view(B, H, W), "mask": mask.view(B, H, W), "depth": depth.view(B, H, W),
+            "normal": n.view(B, H, W, 3),
+            "image": _shade(mask, n, d[None], background).view(B, H, W, 3),
+            "origins": o, "dirs": d}
+
+
+def estimate_lipschitz(decoder, latents: torch.Tensor, resolution: int = 32, *,
+                       bbox: Tuple[float, float] = (-1.0, 1.0),
+                       dtype: str = "fp16") -> torch.Tensor:
+    """The largest gradient norm ``|grad sdf|`` that ``sdf_grad`` finds on a ``resolution^3``
+    grid over ``bbox^3``, per shape: ``[B]``.  An ESTIMATE FROM SAMPLES, NOT A BOUND: the
+    gradient of a ReLU network is piecewise constant and a steeper piece can lie between the
+    samples, so multiply by a margin before using it as ``trace_sdf``'s or ``decode_band``'s
+    ``lipschitz``."""
+    from .grad import sdf_grad
+    capi.require_device(latents)
+    if int(resolution) < 2:
+        raise ValueError("resolution must be >= 2")
+    if latents.dim() == 1:
+        latents = latents[None]
+    xyz = ops.grid_coords(int(resolution), bbox=bbox, device=latents.device)
+    _, g = sdf_grad(decoder, latents, xyz, dtype=dtype)
+    return g.norm(dim=-1).amax(dim=1)
 
 
 # ------------------------------------------------------------------------------------ PNG
