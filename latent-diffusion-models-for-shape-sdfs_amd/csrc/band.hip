@@ -20,13 +20,14 @@
 // Passes (all on the caller's stream, nothing read back to the host):
 //   band_lattice_coords_kernel  [(nb+1)^3][3] coordinates for the points-mode decode
 //   band_classify_kernel        one thread per brick -> active[g] (uint8)
-//   band_block_sums_kernel      per chunk of 4096 bricks: the number of active ones
-//   band_chunk_scan_kernel      one workgroup: exclusive chunk offsets + the total (the count)
-//   band_compact_kernel         per chunk: in-chunk scan, the active global ids in ascending order
+//   flag_compact (flag_compact.h)  the active global ids in ascending order and their number:
+//                               block sums per chunk of 4096 bricks, chunk scan, scatter; one
+//                               segment of B nb^3 flags
 //   band_fill_kernel            a sweep over the dense rows, 4 voxels per thread
-// The compaction is the block-sums + scan form of mc.hip (no atomic append): the list is a pure
-// function of `active`, whatever the scheduling.
+// The compaction has no atomic append: the list is a pure function of `active`, whatever the
+// scheduling.
 #include "decoder_common.h"
+#include "flag_compact.h"
 
 namespace ldm {
 namespace {
@@ -78,90 +79,6 @@ __global__ __launch_bounds__(256) void band_classify_kernel(const float* __restr
     active[g] = (near || !fin || (above && below)) ? 1 : 0;
 }
 
-// bricks per thread of the scan passes (one 16-byte vector of flags), a chunk = 256 threads
-constexpr int kPer = 16;
-constexpr int kChunk = 256 * kPer;
-
-// this thread's 16 flags of chunk `blk` as a bit mask (zeros past n)
-__device__ __forceinline__ unsigned load_flags(const uint8_t* __restrict__ active, int n, int blk) {
-    const int64_t p0 = (int64_t)blk * kChunk + threadIdx.x * kPer;
-    unsigned m = 0;
-    if (p0 + kPer <= n) {
-        const u32x4 a = *reinterpret_cast<const u32x4*>(active + p0);
-#pragma unroll
-        for (int q = 0; q < kPer; ++q) m |= (((a[q >> 2] >> (8 * (q & 3))) & 0xffu) ? 1u : 0u) << q;
-    } else {
-#pragma unroll
-        for (int q = 0; q < kPer; ++q) m |= ((p0 + q < n && active[p0 + q]) ? 1u : 0u) << q;
-    }
-    return m;
-}
-
-// block-wide exclusive scan of one int per thread (256 threads); returns the block total
-__device__ __forceinline__ int block_excl_scan(int v, int* lds /*[4]*/, int* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) lds[wv] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        if (w < wv) base += lds[w];
-        tot += lds[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
-
-__global__ __launch_bounds__(256) void band_block_sums_kernel(const uint8_t* __restrict__ active,
-                                                              int n, int* __restrict__ bsum) {
-    __shared__ int lds[4];
-    int tot;
-    block_excl_scan(__popc(load_flags(active, n, blockIdx.x)), lds, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-// exclusive scan of the chunk sums by one workgroup (thread t owns the chunks [t per, (t+1) per),
-// summed serially, one block scan of the 256 thread sums, a second serial pass writes the
-// offsets) + the total = the number of active bricks
-__global__ __launch_bounds__(256) void band_chunk_scan_kernel(const int* __restrict__ bsum, int nblk,
-                                                              int* __restrict__ boff,
-                                                              int32_t* __restrict__ count) {
-    __shared__ int lds[4];
-    const int per = (nblk + 255) / 256;
-    const int b0 = min((int)threadIdx.x * per, nblk), b1 = min(b0 + per, nblk);
-    int s = 0;
-    for (int b = b0; b < b1; ++b) s += bsum[b];
-    int tot;
-    int c = block_excl_scan(s, lds, &tot);
-    for (int b = b0; b < b1; ++b) {
-        boff[b] = c;
-        c += bsum[b];
-    }
-    if (threadIdx.x == 0) count[0] = tot;
-}
-
-__global__ __launch_bounds__(256) void band_compact_kernel(const uint8_t* __restrict__ active,
-                                                           int n, const int* __restrict__ boff,
-                                                           int32_t* __restrict__ bricks) {
-    __shared__ int lds[4];
-    unsigned m = load_flags(active, n, blockIdx.x);
-    int tot;
-    int off = boff[blockIdx.x] + block_excl_scan(__popc(m), lds, &tot);
-    const int p0 = blockIdx.x * kChunk + threadIdx.x * kPer;   // an active flag: p0 + q < n < 2^31
-    while (m) {
-        const int q = __builtin_ctz(m);
-        m &= m - 1u;
-        bricks[off++] = p0 + q;     // off < the number of active bricks <= n
-    }
-}
-
 // Fill: thread -> 4 consecutive voxels of a dense row (they share a brick: 4 divides 8), quads
 // in (shape, k, j, quad) order so a wave writes 1 KiB of a row; one 16-byte store when rows are
 // 16-byte aligned (N % 4 == 0), else up to 4 scalar stores clipped at N.  A grid-stride loop: the
@@ -195,26 +112,6 @@ __global__ __launch_bounds__(256) void band_fill_kernel(const float* __restrict_
     }
 }
 
-struct BandWs {
-    int* bsum;
-    int* boff;
-    size_t bytes;
-};
-
-BandWs band_ws_layout(int64_t total, void* base) {
-    const int64_t nblk = (total + kChunk - 1) / kChunk;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    BandWs w{};
-    char* b = reinterpret_cast<char*>(base);
-    size_t o = 0;
-    w.bsum = reinterpret_cast<int*>(b + o);
-    o += up((size_t)nblk * sizeof(int));
-    w.boff = reinterpret_cast<int*>(b + o);
-    o += up((size_t)nblk * sizeof(int));
-    w.bytes = o;
-    return w;
-}
-
 // B >= 1, N >= 2 and B nb^3 < 2^31; the brick count through *total
 int check_band_dims(const char* what, int B, int N, int64_t* total) {
     LDM_REQUIRE(N >= 2, LDM_EINVAL, "%s: N = %d < 2", what, N);
@@ -237,7 +134,7 @@ extern "C" size_t ldm_band_workspace_bytes(int B, int N) {
     const int64_t nb = band_nb(N);
     if (nb * nb * nb > (int64_t)0x7fffffff / B) return 0;
     total = (int64_t)B * nb * nb * nb;
-    return band_ws_layout(total, nullptr).bytes;
+    return flag_compact_ws(1, total, nullptr).bytes;
 }
 
 extern "C" int ldm_band_lattice_coords(int N, float vs, float origin, float* xyz_out,
@@ -265,19 +162,14 @@ extern "C" int ldm_band_classify(const float* coarse, int B, int N, float level,
                     LDM_ALIGNED(count, 4) && LDM_ALIGNED(ws, 256),
                 LDM_EALIGN, "ldm_band_classify: active must be 16-byte, the workspace 256-byte "
                 "aligned");
-    const BandWs w = band_ws_layout(total, ws);
+    const FlagCompactWs w = flag_compact_ws(1, total, ws);
     LDM_REQUIRE(ws_bytes >= w.bytes, LDM_ENOSPC, "ldm_band_classify: workspace %zu < %zu B",
                 ws_bytes, w.bytes);
     const int n = (int)total, nb = band_nb(N);
-    const int nblk = (n + kChunk - 1) / kChunk;
     hipStream_t st = (hipStream_t)s;
     hipLaunchKernelGGL(band_classify_kernel, dim3((n + 255) / 256), dim3(256), 0, st, coarse, nb,
                        n, level, band, active);
-    hipLaunchKernelGGL(band_block_sums_kernel, dim3(nblk), dim3(256), 0, st, active, n, w.bsum);
-    hipLaunchKernelGGL(band_chunk_scan_kernel, dim3(1), dim3(256), 0, st, w.bsum, nblk, w.boff,
-                       count);
-    hipLaunchKernelGGL(band_compact_kernel, dim3(nblk), dim3(256), 0, st, active, n, w.boff,
-                       bricks);
+    flag_compact(active, 1, n, w, bricks, count, st);   // active is 16-byte aligned: vector loads
     return launch_status("ldm_band_classify");
 }
 

@@ -251,7 +251,6 @@ __global__ __launch_bounds__(kThreads) void chamfer_reduce_kernel(const float* _
     }
 }
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int64_t n_chunks(int64_t Q) { return (Q + kChunkB - 1) / kChunkB; }
 inline bool use_split(int64_t P, int64_t Q) { return P < kSplitBelow && n_chunks(Q) > 1; }
 inline int n_split(int64_t Q) { return (int)min(n_chunks(Q), (int64_t)kMaxSplit); }

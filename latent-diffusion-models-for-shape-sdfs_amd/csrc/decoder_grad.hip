@@ -499,8 +499,6 @@ __global__ void fold_bwd_kernel(const float* __restrict__ wz, const float* __res
     dz[id] = (float)acc;
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // tiles of a launch, 0 when the sizes are invalid
 long long grad_tiles(int B, int P) {
     if (B < 1 || P < 1 || B > 65535 || (long long)B * P >= (1ll << 31)) return 0;

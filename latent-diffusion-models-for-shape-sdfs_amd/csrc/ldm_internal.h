@@ -47,6 +47,9 @@ int set_max_lds_once(int bytes, const char* what) {
 
 #define LDM_ALIGNED(p, a) ((((uintptr_t)(p)) & ((a) - 1)) == 0)
 
+// workspace sub-buffers start at multiples of 256 bytes
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 // Device-side invariant checks: compiled in by `make DEBUG=1` (-DLDM_DEBUG), where a failed
 // check prints its location and traps the kernel (an error the host sees at the next
 // synchronisation); the product build compiles them out.

@@ -19,7 +19,7 @@
 //                 through vofs + the owner's mask
 // Vertex order = (owner point, axis); face order = (cube, table order): a pure function of
 // the volume, so the output is deterministic and equal to the oracle's.
-#include "ldm_internal.h"
+#include "flag_compact.h"   // block_excl_scan
 
 #include <string.h>
 
@@ -244,28 +244,6 @@ __global__ __launch_bounds__(256) void mc_classify_kernel(const float* __restric
 
 __device__ __forceinline__ int nvert_of(unsigned c) { return __popc(c & 7u); }
 __device__ __forceinline__ int ntri_of(unsigned c) { return (c >> 3) & 7u; }
-
-// block-wide exclusive scan of one int per thread (256 threads); returns the block total
-__device__ __forceinline__ int block_excl_scan(int v, int* lds /*[4]*/, int* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) lds[wv] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        if (w < wv) base += lds[w];
-        tot += lds[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
 
 // load the kPer codes of this thread's slice of chunk `blk` (zeros past n)
 __device__ __forceinline__ void load_codes(const unsigned short* __restrict__ code, int64_t n,
@@ -534,18 +512,17 @@ struct McWs {
 McWs mc_ws_layout(int N, void* base) {
     const int64_t n = (int64_t)N * N * N;
     const int64_t nb = (n + kChunk - 1) / kChunk;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     McWs w{};
     char* b = reinterpret_cast<char*>(base);
     size_t o = 0;
     w.code = reinterpret_cast<unsigned short*>(b + o);
-    o += up((size_t)nb * kChunk * 2);           // padded to whole chunks (vector loads)
+    o += up256((size_t)nb * kChunk * 2);           // padded to whole chunks (vector loads)
     w.bsum = reinterpret_cast<int2*>(b + o);
-    o += up((size_t)nb * sizeof(int2));
+    o += up256((size_t)nb * sizeof(int2));
     w.boff = reinterpret_cast<int2*>(b + o);
-    o += up((size_t)nb * sizeof(int2));
+    o += up256((size_t)nb * sizeof(int2));
     w.vofs = reinterpret_cast<int32_t*>(b + o);
-    o += up((size_t)n * 4);
+    o += up256((size_t)n * 4);
     w.bytes = o;
     return w;
 }

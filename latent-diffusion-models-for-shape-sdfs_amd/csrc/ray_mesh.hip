@@ -1,13 +1,15 @@
 // Closest intersection of many rays with a triangle soup, MI355X (gfx950).  DESIGN.md §19.
 //
-// The sibling of mesh_sdf.hip: every ray against every face, no acceleration structure.  Per
+// The sibling of mesh_sdf.hip, with which it shares soup_plan.h (the face loader, the switch
+// between the launch forms, the workspace, the argument checks): every ray against every face,
+// no acceleration structure.  Per
 // ray: the smallest t in [t_min, t_max] with o + t d on a triangle, that triangle's index
 // (ties to the smaller index) and the barycentric weights of the hit.  The pair arithmetic is
 // the watertight test of ray_tri_pair.h.
 //
 // Kernels (all fp32 VALU; no LDS, no barrier, no float atomics):
-//   pack     one thread per face: indices clamped to [0, V) (a clamp raises *flag), the 48-byte
-//            record RayTri written to the workspace
+//   pack     one thread per face: the face loaded by soup_load_face (indices clamped to
+//            [0, V), a clamp raises *flag), the 48-byte record RayTri written to the workspace
 //   trace    256 threads, one ray per thread held in registers.  The triangle record is read
 //            at a wave-uniform address (loop counter + blockIdx only): the compiler turns that
 //            into scalar loads, and the record feeds the VALU from SGPRs.  The axis
@@ -23,7 +25,7 @@
 //   split form     (R <  kSplitBelow)  grid.y = chunks of kFaceChunk faces, partials (t, face)
 //                  to the workspace per tile of kSplitTile rays, then combine
 // Both forms give a ray bitwise the same outputs, alone or among a million others.
-#include "ldm_internal.h"
+#include "soup_plan.h"
 #include "ray_tri_pair.h"
 
 namespace ldm {
@@ -48,20 +50,8 @@ __global__ __launch_bounds__(kThreads) void ray_pack_kernel(const float* __restr
                                                             int32_t* __restrict__ flag) {
     const int64_t f = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (f >= F) return;
-    int id[3];
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int raw = faces[f * 3 + k];
-        id[k] = min(max(raw, 0), V - 1);
-        bad = bad || id[k] != raw;
-    }
-    if (bad) atomicOr(flag, 1);
     float p[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) p[k][c] = verts[(int64_t)id[k] * 3 + c];
+    soup_load_face(verts, V, faces, f, flag, p);
     RayTri T;
     T.ax = p[0][0]; T.ay = p[0][1]; T.az = p[0][2];
     T.bx = p[1][0]; T.by = p[1][1]; T.bz = p[1][2];
@@ -169,10 +159,9 @@ __global__ __launch_bounds__(kThreads) void ray_combine_kernel(
     ray_finish(tri, r, t_min, t_max, best, bface, i, t_out, face_out, bary_out);
 }
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline int n_chunks(int F) { return (F + kFaceChunk - 1) / kFaceChunk; }
-inline bool use_split(int F, int64_t R) { return R < kSplitBelow && n_chunks(F) > 1; }
-inline size_t tri_bytes(int F) { return up256((size_t)F * sizeof(RayTri)); }
+SoupPlan ray_plan(int F, int64_t R) {
+    return soup_plan(kFaceChunk, kSplitBelow, kSplitTile, sizeof(RayTri), sizeof(Partial), F, R);
+}
 
 }  // namespace
 }  // namespace ldm
@@ -181,12 +170,7 @@ extern "C" int ldm_ray_mesh_face_chunk(void) { return ldm::kFaceChunk; }
 extern "C" int64_t ldm_ray_mesh_split_below(void) { return ldm::kSplitBelow; }
 
 extern "C" size_t ldm_ray_mesh_ws_bytes(int F, int64_t R) {
-    using namespace ldm;
-    if (F < 0 || R < 0) return 0;
-    size_t b = 256 + tri_bytes(F);
-    if (use_split(F, R))
-        b += up256((size_t)n_chunks(F) * (size_t)min((int64_t)kSplitTile, R) * sizeof(Partial));
-    return b;
+    return F < 0 || R < 0 ? 0 : ldm::ray_plan(F, R).ws_bytes;
 }
 
 extern "C" int ldm_ray_mesh(const float* verts, int V, const int32_t* faces, int F,
@@ -194,57 +178,42 @@ extern "C" int ldm_ray_mesh(const float* verts, int V, const int32_t* faces, int
                             float t_max, float* t_out, int32_t* face_out, float* bary_out,
                             int32_t* flag, void* ws, size_t ws_bytes, ldm_stream_t s) {
     using namespace ldm;
-    LDM_REQUIRE(V >= 0 && F >= 0 && R >= 0, LDM_EINVAL,
-                "ldm_ray_mesh: negative size (V = %d, F = %d, R = %lld)", V, F, (long long)R);
-    LDM_REQUIRE(t_min <= t_max, LDM_EINVAL,
+    // the range comes second: a negative size is left to soup_check_args, which reports it first
+    LDM_REQUIRE(V < 0 || F < 0 || R < 0 || t_min <= t_max, LDM_EINVAL,
                 "ldm_ray_mesh: t_min = %g, t_max = %g: need t_min <= t_max, neither a NaN",
                 (double)t_min, (double)t_max);
+    const SoupPlan plan = ray_plan(F, R);
+    LDM_TRY(soup_check_args(
+        "ldm_ray_mesh", 'R', plan, V, verts, faces, origins && dirs && t_out && flag && ws,
+        "origins / dirs / t_out / flag / workspace",
+        LDM_ALIGNED(origins, 4) && LDM_ALIGNED(dirs, 4) && LDM_ALIGNED(t_out, 4) &&
+            LDM_ALIGNED(face_out, 4) && LDM_ALIGNED(bary_out, 4) && LDM_ALIGNED(flag, 4) &&
+            LDM_ALIGNED(verts, 4) && LDM_ALIGNED(faces, 4) && LDM_ALIGNED(ws, 256),
+        ws_bytes));
     if (R == 0) return 0;
-    LDM_REQUIRE(origins && dirs && t_out && flag && ws, LDM_EINVAL,
-                "ldm_ray_mesh: NULL origins / dirs / t_out / flag / workspace");
-    LDM_REQUIRE(F == 0 || (verts && faces && V > 0), LDM_EINVAL,
-                "ldm_ray_mesh: %d faces need vertices (V = %d) and indices", F, V);
-    LDM_REQUIRE(LDM_ALIGNED(origins, 4) && LDM_ALIGNED(dirs, 4) && LDM_ALIGNED(t_out, 4) &&
-                    LDM_ALIGNED(face_out, 4) && LDM_ALIGNED(bary_out, 4) &&
-                    LDM_ALIGNED(flag, 4) && LDM_ALIGNED(verts, 4) && LDM_ALIGNED(faces, 4) &&
-                    LDM_ALIGNED(ws, 256),
-                LDM_EALIGN, "ldm_ray_mesh: tensors must be 4-B, the workspace 256-B aligned");
-    const size_t need = ldm_ray_mesh_ws_bytes(F, R);
-    LDM_REQUIRE(ws_bytes >= need, LDM_ENOSPC, "ldm_ray_mesh: workspace %zu < %zu B", ws_bytes,
-                need);
-    // the grids of both forms, checked with the arguments: nothing is queued before a refusal
-    const bool split = use_split(F, R);
-    const int64_t blocks = (R + kThreads - 1) / kThreads;
-    LDM_REQUIRE(split || blocks <= 0x7fffffff, LDM_EINVAL,
-                "ldm_ray_mesh: R = %lld needs more than 2^31 - 1 workgroups", (long long)R);
-    const int nchunk = n_chunks(F);
-    LDM_REQUIRE(!split || nchunk <= 65535, LDM_EINVAL,
-                "ldm_ray_mesh: F = %d is %d chunks, above the 65535 of grid.y, with R = %lld "
-                "below %lld", F, nchunk, (long long)R, (long long)kSplitBelow);
     hipStream_t st = (hipStream_t)s;
     RayTri* tri = reinterpret_cast<RayTri*>(ws);
-    Partial* part = reinterpret_cast<Partial*>(reinterpret_cast<char*>(ws) + tri_bytes(F));
+    Partial* part = reinterpret_cast<Partial*>(reinterpret_cast<char*>(ws) + plan.tri_bytes);
     const hipError_t e = hipMemsetAsync(flag, 0, sizeof(int32_t), st);
     LDM_REQUIRE(e == hipSuccess, (int)e, "ldm_ray_mesh: memset: %s", hipGetErrorString(e));
     if (F > 0)
         hipLaunchKernelGGL(ray_pack_kernel, dim3((unsigned)((F + kThreads - 1) / kThreads)),
                            dim3(kThreads), 0, st, verts, V, faces, F, tri, flag);
-    if (!split) {
-        hipLaunchKernelGGL((ray_trace_kernel<false>), dim3((unsigned)blocks), dim3(kThreads), 0,
-                           st, tri, F, origins, dirs, R, t_min, t_max, t_out, face_out, bary_out,
-                           (Partial*)nullptr, 0);
+    if (!plan.split) {
+        hipLaunchKernelGGL((ray_trace_kernel<false>), dim3((unsigned)plan.blocks), dim3(kThreads),
+                           0, st, tri, F, origins, dirs, R, t_min, t_max, t_out, face_out,
+                           bary_out, (Partial*)nullptr, 0);
         return launch_status("ldm_ray_mesh");
     }
-    const int stride = (int)min((int64_t)kSplitTile, R);
     for (int64_t r0 = 0; r0 < R; r0 += kSplitTile) {
         const int n = (int)min((int64_t)kSplitTile, R - r0);
         const unsigned gx = (unsigned)((n + kThreads - 1) / kThreads);
-        hipLaunchKernelGGL((ray_trace_kernel<true>), dim3(gx, (unsigned)nchunk), dim3(kThreads),
-                           0, st, tri, F, origins + r0 * 3, dirs + r0 * 3, (int64_t)n, t_min,
-                           t_max, (float*)nullptr, (int32_t*)nullptr, (float*)nullptr, part,
-                           stride);
-        hipLaunchKernelGGL(ray_combine_kernel, dim3(gx), dim3(kThreads), 0, st, part, nchunk,
-                           stride, tri, origins + r0 * 3, dirs + r0 * 3, n, t_min, t_max,
+        hipLaunchKernelGGL((ray_trace_kernel<true>), dim3(gx, (unsigned)plan.nchunk),
+                           dim3(kThreads), 0, st, tri, F, origins + r0 * 3, dirs + r0 * 3,
+                           (int64_t)n, t_min, t_max, (float*)nullptr, (int32_t*)nullptr,
+                           (float*)nullptr, part, plan.tile_stride);
+        hipLaunchKernelGGL(ray_combine_kernel, dim3(gx), dim3(kThreads), 0, st, part, plan.nchunk,
+                           plan.tile_stride, tri, origins + r0 * 3, dirs + r0 * 3, n, t_min, t_max,
                            t_out + r0, face_out ? face_out + r0 : nullptr,
                            bary_out ? bary_out + r0 * 3 : nullptr);
     }

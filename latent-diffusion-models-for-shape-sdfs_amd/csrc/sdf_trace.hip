@@ -7,48 +7,39 @@
 //            (ray_brick_dda.h), t / t_end / status / steps, the ray's "still marching" flag
 //   step     per listed ray: the decoder value of its point -> hit, miss or a longer t (and the
 //            walk through inactive bricks), the flag rewritten
-//   compact  per shape, the block-sums + scan + scatter form of band.hip: the marching rays'
-//            indices in ascending order and their number -- a pure function of the flags
+//   compact  flag_compact.h with one segment per shape: the marching rays' indices in
+//            ascending order and their number -- a pure function of the flags
 //   emit     the next round's points o + t d as [B][P][3]; a shorter shape's padding slots
 //            repeat its last listed point (a shape with none gets the box corner)
 // Plain fp32 VALU and vector stores; no atomics, no workgroup waits on another; everything on
 // the caller's stream.  The host reads the B counts once per round -- the loop's only
 // synchronisation -- and that read is the caller's (ldm_sdf/render.py).
-#include "ldm_internal.h"
+#include "flag_compact.h"
 #include "ray_brick_dda.h"
 
 namespace ldm {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kPer = 16;                    // flags per thread of the scan passes
-constexpr int kChunk = kThreads * kPer;     // rays per scan chunk
 
 struct TraceWs {
     float* t_end;       // [B R]
     uint8_t* flags;     // [B R] 1: still marching
-    int* bsum;          // [B][nchunk]
-    int* boff;          // [B][nchunk]
+    FlagCompactWs scan; // the compaction's chunk sums and offsets, B segments of R flags
     size_t bytes;
 };
 
-inline int64_t n_chunks(int64_t R) { return (R + kChunk - 1) / kChunk; }
-
 TraceWs trace_ws_layout(int B, int64_t R, void* base) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t n = (size_t)B * (size_t)R, nc = (size_t)B * (size_t)n_chunks(R);
+    const size_t n = (size_t)B * (size_t)R;
     TraceWs w{};
     char* b = reinterpret_cast<char*>(base);
     size_t o = 0;
     w.t_end = reinterpret_cast<float*>(b + o);
-    o += up(n * sizeof(float));
+    o += up256(n * sizeof(float));
     w.flags = reinterpret_cast<uint8_t*>(b + o);
-    o += up(n);
-    w.bsum = reinterpret_cast<int*>(b + o);
-    o += up(nc * sizeof(int));
-    w.boff = reinterpret_cast<int*>(b + o);
-    o += up(nc * sizeof(int));
-    w.bytes = o;
+    o += up256(n);
+    w.scan = flag_compact_ws(B, R, b + o);
+    w.bytes = o + w.scan.bytes;
     return w;
 }
 
@@ -137,84 +128,6 @@ __global__ __launch_bounds__(kThreads) void trace_step_kernel(
     t[s] = st == rbd::kMiss ? INFINITY : tt;
 }
 
-// this thread's 16 flags of chunk `chunk` of one shape as a bit mask (zeros past R)
-__device__ __forceinline__ unsigned load_flags(const uint8_t* __restrict__ f, int R, int chunk) {
-    const int p0 = chunk * kChunk + threadIdx.x * kPer;       // < R + kChunk: no overflow
-    unsigned m = 0;
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) m |= ((p0 + u < R && f[p0 + u]) ? 1u : 0u) << u;
-    return m;
-}
-
-// block-wide exclusive scan of one int per thread (256 threads); the block total through *total
-__device__ __forceinline__ int block_excl_scan(int v, int* lds /*[4]*/, int* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) lds[wv] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        if (w < wv) base += lds[w];
-        tot += lds[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
-
-// grid (nchunk, B)
-__global__ __launch_bounds__(kThreads) void trace_block_sums_kernel(
-    const uint8_t* __restrict__ flags, int R, int* __restrict__ bsum) {
-    __shared__ int lds[4];
-    int tot;
-    block_excl_scan(__popc(load_flags(flags + (int64_t)blockIdx.y * R, R, blockIdx.x)), lds, &tot);
-    if (threadIdx.x == 0) bsum[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = tot;
-}
-
-// grid (B): one workgroup scans one shape's chunk sums; counts[b] = its marching rays
-__global__ __launch_bounds__(kThreads) void trace_chunk_scan_kernel(
-    const int* __restrict__ bsum, int nchunk, int* __restrict__ boff,
-    int32_t* __restrict__ counts) {
-    __shared__ int lds[4];
-    const int* in = bsum + (int64_t)blockIdx.x * nchunk;
-    int* out = boff + (int64_t)blockIdx.x * nchunk;
-    const int per = (nchunk + kThreads - 1) / kThreads;
-    const int b0 = min((int)threadIdx.x * per, nchunk), b1 = min(b0 + per, nchunk);
-    int sum = 0;
-    for (int c = b0; c < b1; ++c) sum += in[c];
-    int tot;
-    int c0 = block_excl_scan(sum, lds, &tot);
-    for (int c = b0; c < b1; ++c) {
-        out[c] = c0;
-        c0 += in[c];
-    }
-    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
-}
-
-// grid (nchunk, B)
-__global__ __launch_bounds__(kThreads) void trace_scatter_kernel(
-    const uint8_t* __restrict__ flags, int R, const int* __restrict__ boff,
-    int32_t* __restrict__ list) {
-    __shared__ int lds[4];
-    unsigned m = load_flags(flags + (int64_t)blockIdx.y * R, R, blockIdx.x);
-    int tot;
-    int off = boff[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] +
-              block_excl_scan(__popc(m), lds, &tot);
-    const int p0 = blockIdx.x * kChunk + threadIdx.x * kPer;
-    int32_t* dst = list + (int64_t)blockIdx.y * R;
-    while (m) {
-        const int u = __builtin_ctz(m);
-        m &= m - 1u;
-        dst[off++] = p0 + u;     // off < this shape's count <= R
-    }
-}
-
 // grid (ceil(P / 256), B)
 __global__ __launch_bounds__(kThreads) void trace_emit_kernel(
     Rays q, int R, int P, const float* __restrict__ t, const int32_t* __restrict__ list,
@@ -239,9 +152,9 @@ int check_dims(const char* what, int B, int64_t R) {
     LDM_REQUIRE(R >= 1, LDM_EINVAL, "%s: R = %lld < 1", what, (long long)R);
     LDM_REQUIRE(R <= (int64_t)0x7fffffff / B, LDM_EINVAL,
                 "%s: B * R = %d * %lld does not fit 31 bits", what, B, (long long)R);
-    LDM_REQUIRE(n_chunks(R) <= 65535 && B <= 65535, LDM_EINVAL,
+    LDM_REQUIRE(flag_chunks(R) <= 65535 && B <= 65535, LDM_EINVAL,
                 "%s: B = %d shapes or %lld chunks of rays exceed the 65535 of a grid axis", what,
-                B, (long long)n_chunks(R));
+                B, (long long)flag_chunks(R));
     return 0;
 }
 
@@ -268,17 +181,6 @@ int check_march(const char* what, float level, float lipschitz, float eps) {
                 "%s: lipschitz = %g must be positive and finite", what, (double)lipschitz);
     LDM_REQUIRE(level == level, LDM_EINVAL, "%s: level is a NaN", what);
     return 0;
-}
-
-void launch_compact(const TraceWs& w, int B, int R, int32_t* list, int32_t* counts,
-                    hipStream_t st) {
-    const int nchunk = (int)n_chunks(R);
-    hipLaunchKernelGGL(trace_block_sums_kernel, dim3(nchunk, B), dim3(kThreads), 0, st, w.flags,
-                       R, w.bsum);
-    hipLaunchKernelGGL(trace_chunk_scan_kernel, dim3(B), dim3(kThreads), 0, st, w.bsum, nchunk,
-                       w.boff, counts);
-    hipLaunchKernelGGL(trace_scatter_kernel, dim3(nchunk, B), dim3(kThreads), 0, st, w.flags, R,
-                       w.boff, list);
 }
 
 }  // namespace
@@ -324,7 +226,7 @@ extern "C" int ldm_sdf_trace_init(const float* origins, const float* dirs, int p
     hipLaunchKernelGGL(trace_init_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)),
                        dim3(kThreads), 0, st, q, B, (int)R, lo, hi, t_min, t_max, g, t, w.t_end,
                        status, steps, xyz_last, w.flags);
-    launch_compact(w, B, (int)R, list, counts, st);
+    flag_compact(w.flags, B, (int)R, w.scan, list, counts, st);
     return launch_status(what);
 }
 
@@ -379,6 +281,6 @@ extern "C" int ldm_sdf_trace_step(const float* origins, const float* dirs, int p
     hipLaunchKernelGGL(trace_step_kernel, dim3((unsigned)((P + kThreads - 1) / kThreads), B),
                        dim3(kThreads), 0, st, q, (int)R, P, vals, list, counts, level, lipschitz,
                        eps, g, t, w.t_end, status, steps, xyz_last, w.flags);
-    launch_compact(w, B, (int)R, list, counts, st);
+    flag_compact(w.flags, B, (int)R, w.scan, list, counts, st);
     return launch_status(what);
 }

@@ -8,7 +8,7 @@ one shape against the marching-cubes mesh of a 256^3 volume (~10^5 faces), every
               rate in pairs/s is what is compared), 1 warm-up and the median of 3
 Reports pairs/s, the agreement of the two, and the fraction of the fp32 VALU issue rate that the
 kernel's inner loop implies: VALU_PER_PAIR instructions per pair, counted from `make asm`
-(csrc/build/mesh_sdf.s, the loop of mesh_eval_kernel<1, false>), each wave64
+(csrc/build/mesh_sdf.s, the loop of mesh_eval_kernel<false>), each wave64
 instruction taking 2 cycles of its SIMD; ISSUE_SLOTS_PER_PAIR counts the packed fp32 and the
 transcendental instructions twice.  Prints one JSON line; --out also writes it to a file.
 

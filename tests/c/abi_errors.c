@@ -5,35 +5,17 @@
  * the training step's job table built from descriptors) must work.  No GPU is needed: argument
  * checks run before any device work, and the device queries fail cleanly without one.
  * (Test infrastructure; SURVEY.md §5 "Sanitizers".) */
-#include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "ldm_sdf.h"
+#include "check.h"
 
-static int fails = 0, checks = 0;
-#define EXPECT(cond)                                                               \
-    do {                                                                           \
-        ++checks;                                                                  \
-        if (!(cond)) {                                                             \
-            ++fails;                                                               \
-            fprintf(stderr, "FAIL %s:%d: %s (last error: %s)\n", __FILE__, __LINE__, \
-                    #cond, ldm_last_error());                                      \
-        }                                                                          \
-    } while (0)
 #define EXPECT_ERR(expr)                                                          \
     do {                                                                          \
         const int rc_ = (expr);                                                   \
         EXPECT(rc_ != 0);                                                         \
         EXPECT(ldm_last_error() != NULL && ldm_last_error()[0] != 0);             \
     } while (0)
-
-static uintptr_t fake_next = 0x7f0000000000ull;
-static void* fake(void) { /* distinct, never dereferenced by host code */
-    fake_next += 0x1000000;
-    return (void*)fake_next;
-}
 
 int main(void) {
     float f[64];
@@ -198,6 +180,5 @@ int main(void) {
     EXPECT(ldm_mc_table(&tri[0][0], ntri) == 0);
     EXPECT(ntri[0] == 0 && ntri[1] == 1 && tri[1][3] == -1);
 
-    printf("abi_errors: %d checks, %d failures\n", checks, fails);
-    return fails ? 1 : 0;
+    return check_report("abi_errors");
 }

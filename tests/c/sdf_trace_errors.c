@@ -5,35 +5,9 @@
  * checks run before any device work.  Built by tests/test_sdf_trace_reference.py against the
  * product library and by csrc/Makefile `check-asan` under host AddressSanitizer. */
 #include <math.h>
-#include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
-#include "ldm_sdf.h"
-
-static int fails = 0, checks = 0;
-#define EXPECT(cond)                                                               \
-    do {                                                                           \
-        ++checks;                                                                  \
-        if (!(cond)) {                                                             \
-            ++fails;                                                               \
-            fprintf(stderr, "FAIL %s:%d: %s (last error: %s)\n", __FILE__, __LINE__, \
-                    #cond, ldm_last_error());                                      \
-        }                                                                          \
-    } while (0)
-#define EXPECT_RC(expr, code)                                                     \
-    do {                                                                          \
-        const int rc_ = (expr);                                                   \
-        EXPECT(rc_ == (code));                                                    \
-        EXPECT(ldm_last_error() != NULL && ldm_last_error()[0] != 0);             \
-    } while (0)
-
-static uintptr_t fake_next = 0x7f0000000000ull;
-static void* fake(void) { /* distinct, 4 KiB aligned, never dereferenced by host code */
-    fake_next += 0x1000000;
-    return (void*)fake_next;
-}
-static void* off(void* p, int bytes) { return (void*)((uintptr_t)p + (uintptr_t)bytes); }
+#include "check.h"
 
 int main(void) {
     float* o = (float*)fake();
@@ -208,6 +182,5 @@ int main(void) {
     EXPECT_RC(STEP(o, d, B, R, P, va, -1.f, 0.f, 1.f, 1e-3f, mk, N, vs, t, st, sp, NULL, li, cn,
                    ws, 16), LDM_ENOSPC);
 
-    printf("sdf_trace_errors: %d checks, %d failures\n", checks, fails);
-    return fails ? 1 : 0;
+    return check_report("sdf_trace_errors");
 }

@@ -4,35 +4,9 @@
  * ldm_last_error() -- never crash, read or write out of bounds.  No GPU is needed: the argument
  * checks run before any device work.  Built by tests/test_unet_train_host.py against the product
  * library and by csrc/Makefile `check-asan` under host AddressSanitizer. */
-#include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
-#include "ldm_sdf.h"
-
-static int fails = 0, checks = 0;
-#define EXPECT(cond)                                                               \
-    do {                                                                           \
-        ++checks;                                                                  \
-        if (!(cond)) {                                                             \
-            ++fails;                                                               \
-            fprintf(stderr, "FAIL %s:%d: %s (last error: %s)\n", __FILE__, __LINE__, \
-                    #cond, ldm_last_error());                                      \
-        }                                                                          \
-    } while (0)
-#define EXPECT_RC(expr, code)                                                     \
-    do {                                                                          \
-        const int rc_ = (expr);                                                   \
-        EXPECT(rc_ == (code));                                                    \
-        EXPECT(ldm_last_error() != NULL && ldm_last_error()[0] != 0);             \
-    } while (0)
-
-static uintptr_t fake_next = 0x7f0000000000ull;
-static void* fake(void) { /* distinct, 4 KiB aligned, never dereferenced by host code */
-    fake_next += 0x1000000;
-    return (void*)fake_next;
-}
-static void* off(const void* p, int bytes) { return (void*)((uintptr_t)p + (uintptr_t)bytes); }
+#include "check.h"
 
 /* a k = 3, stride 1, pad 1 segment of 40 channels (packed row of 48) over 130 positions */
 static ldm_conv1d_seg_t good_seg(void) {
@@ -187,6 +161,5 @@ int main(void) {
     w = good_weight(); w.ws = NULL;
     EXPECT_RC(ldm_conv1d_bwd_weight(&w, NULL), LDM_ENOSPC);
 
-    printf("unet_bwd_errors: %d checks, %d failures\n", checks, fails);
-    return fails ? 1 : 0;
+    return check_report("unet_bwd_errors");
 }

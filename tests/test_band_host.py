@@ -3,18 +3,14 @@ reference, the workspace size, and the argument checks of every new C-ABI entry 
 Python through ctypes and from C (tests/c/band_errors.c, the source `make check-asan` also runs
 under host AddressSanitizer)."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import band_reference as BR
+from tests.c_checker import run_c_checker
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "latent-diffusion-models-for-shape-sdfs_amd", "ldm_sdf")
 EINVAL, EALIGN, ENOSPC = -22, -14, -28
 A = 0x7f0000000000          # fake device addresses: never dereferenced by the host checks
 
@@ -138,15 +134,4 @@ def test_reference_rule_on_a_hand_case():
 
 
 def test_band_errors_from_c(tmp_path):
-    if not os.path.exists(os.path.join(LIBDIR, "libldm_sdf.so")):
-        pytest.fail("libldm_sdf.so is not built (make -C .../csrc)")
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    exe = str(tmp_path / "band_errors")
-    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c", "band_errors.c"), "-o", exe, "-L", LIBDIR,
-                    "-lldm_sdf", "-Wl,-rpath," + LIBDIR], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "0 failures" in r.stdout
+    run_c_checker("band_errors", tmp_path)

@@ -3,18 +3,13 @@ tests/emd_reference.py, the default round cap against the reference auction's ro
 the exact inputs of tests/test_gpu_emd.py, the argument errors of the Python layer that need no
 GPU, and the C error-path checker tests/c/emd_errors.c (the source `make check-asan` also runs
 under host AddressSanitizer)."""
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import emd_reference as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "latent-diffusion-models-for-shape-sdfs_amd", "ldm_sdf")
+from tests.c_checker import run_c_checker
 
 
 def test_host_functions_agree_with_the_reference():
@@ -77,14 +72,4 @@ def test_unknown_metric_is_refused():
 
 
 def test_emd_errors_from_c(tmp_path):
-    if not os.path.exists(os.path.join(LIBDIR, "libldm_sdf.so")):
-        pytest.fail("libldm_sdf.so is not built (make -C .../csrc)")
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    exe = str(tmp_path / "emd_errors")
-    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c", "emd_errors.c"), "-o", exe, "-L", LIBDIR,
-                    "-lldm_sdf", "-lm", "-Wl,-rpath," + LIBDIR], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
+    run_c_checker("emd_errors", tmp_path)

@@ -90,7 +90,10 @@ def _synthetic_values(B, R, K, level, eps, seed):
 @pytest.mark.parametrize("R,B,per_shape,N", [(1, 1, False, 0), (63, 3, False, 20),
                                              (64, 1, True, 33), (65, 3, True, 0),
                                              (1000, 3, False, 64), (70000, 3, False, 40),
-                                             (70000, 1, False, 0)])
+                                             (70000, 1, False, 0),
+                                             # two scan chunks per shape, shapes 1 and 2 start at
+                                             # flag addresses that are not 16-byte aligned
+                                             (4099, 3, False, 0)])
 def test_kernels_equal_reference_bit_for_bit(dev, R, B, per_shape, N):
     from ldm_sdf import ops
     K, level, lip, eps = 6, -0.1, 0.45, 1e-3

@@ -11,25 +11,15 @@ import numpy as np
 import pytest
 import torch
 
+from tests.c_checker import run_c_checker
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "latent-diffusion-models-for-shape-sdfs_amd", "ldm_sdf")
 EINVAL, EALIGN, ENOSPC, ENOSYS = -22, -14, -28, -38
 A = 0x7f0000000000          # fake device addresses: never dereferenced by the host checks
 
 
 def test_grad_errors_from_c(tmp_path):
-    if not os.path.exists(os.path.join(LIBDIR, "libldm_sdf.so")):
-        pytest.fail("libldm_sdf.so is not built (make -C .../csrc)")
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    exe = str(tmp_path / "grad_errors")
-    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c", "grad_errors.c"), "-o", exe, "-L", LIBDIR,
-                    "-lldm_sdf", "-Wl,-rpath," + LIBDIR], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "0 failures" in r.stdout
+    run_c_checker("grad_errors", tmp_path)
 
 
 @pytest.mark.parametrize("B,P", [(1, 1), (1, 64), (1, 65), (3, 197), (64, 16384), (3, 6000)])

@@ -13,11 +13,11 @@ import torch
 
 from tests import mesh_sdf_reference as M
 from tests import ray_mesh_reference as RR
+from tests.c_checker import run_c_checker
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "latent-diffusion-models-for-shape-sdfs_amd")
 CSRC = os.path.join(PKG, "csrc")
-LIBDIR = os.path.join(PKG, "ldm_sdf")
 
 
 @pytest.fixture(scope="module")
@@ -328,14 +328,4 @@ def test_launch_constants_are_exported():
 
 
 def test_ray_mesh_errors_from_c(tmp_path):
-    if not os.path.exists(os.path.join(LIBDIR, "libldm_sdf.so")):
-        pytest.fail("libldm_sdf.so is not built (make -C .../csrc)")
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    exe = str(tmp_path / "ray_mesh_errors")
-    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c", "ray_mesh_errors.c"), "-o", exe, "-L", LIBDIR,
-                    "-lldm_sdf", "-Wl,-rpath," + LIBDIR], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
+    run_c_checker("ray_mesh_errors", tmp_path)

@@ -4,14 +4,11 @@ are never dereferenced), the workspace size, the pure grouping function behind
 ``sample(form=...)``, and the C error-path checker tests/c/sample_batch_errors.c (the source
 `make check-asan` also runs under host AddressSanitizer)."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "latent-diffusion-models-for-shape-sdfs_amd", "ldm_sdf")
+from tests.c_checker import run_c_checker
+
 
 EINVAL, EALIGN, ENOSYS, ENOSPC = -22, -14, -38, -28
 _next = [0x7f0000000000]
@@ -167,14 +164,4 @@ def test_unknown_form_and_bad_sizes():
 
 
 def test_sample_batch_errors_from_c(tmp_path):
-    if not os.path.exists(os.path.join(LIBDIR, "libldm_sdf.so")):
-        pytest.fail("libldm_sdf.so is not built (make -C .../csrc)")
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    exe = str(tmp_path / "sample_batch_errors")
-    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c", "sample_batch_errors.c"), "-o", exe, "-L",
-                    LIBDIR, "-lldm_sdf", "-Wl,-rpath," + LIBDIR], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
+    run_c_checker("sample_batch_errors", tmp_path)

@@ -14,11 +14,11 @@ import pytest
 import torch
 
 from tests import sdf_trace_reference as T
+from tests.c_checker import run_c_checker
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "latent-diffusion-models-for-shape-sdfs_amd")
 CSRC = os.path.join(PKG, "csrc")
-LIBDIR = os.path.join(PKG, "ldm_sdf")
 F32 = np.float32
 
 
@@ -239,18 +239,7 @@ def test_header_equals_reference_bit_for_bit(dda_check, tmp_path, N, use_mask):
 
 
 def test_sdf_trace_errors_from_c(tmp_path):
-    if not os.path.exists(os.path.join(LIBDIR, "libldm_sdf.so")):
-        pytest.fail("libldm_sdf.so is not built (make -C .../csrc)")
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    exe = str(tmp_path / "sdf_trace_errors")
-    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c", "sdf_trace_errors.c"), "-o", exe, "-L", LIBDIR,
-                    "-lldm_sdf", "-Wl,-rpath," + LIBDIR], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "0 failures" in r.stdout
+    run_c_checker("sdf_trace_errors", tmp_path)
 
 
 # ------------------------------------------------------------------ the Python argument checks

@@ -11,8 +11,9 @@ import subprocess
 import pytest
 import torch
 
+from tests.c_checker import run_c_checker
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "latent-diffusion-models-for-shape-sdfs_amd", "ldm_sdf")
 A = 0x7f0000000000          # fake device addresses: never dereferenced by the host checks
 
 # the GPU tests' tiny nets: (D, C, TE, HT, T, B)
@@ -20,18 +21,7 @@ TINY = [(64, (16, 32, 48), 16, 32, 50, 3), (72, (8, 24, 40), 16, 32, 50, 5)]
 
 
 def test_unet_bwd_errors_from_c(tmp_path):
-    if not os.path.exists(os.path.join(LIBDIR, "libldm_sdf.so")):
-        pytest.fail("libldm_sdf.so is not built (make -C .../csrc)")
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    exe = str(tmp_path / "unet_bwd_errors")
-    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c", "unet_bwd_errors.c"), "-o", exe, "-L", LIBDIR,
-                    "-lldm_sdf", "-Wl,-rpath," + LIBDIR], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "0 failures" in r.stdout
+    run_c_checker("unet_bwd_errors", tmp_path)
 
 
 @pytest.mark.parametrize("shape", [(1, 1, 3), (5, 8, 4), (20, 33, 3), (70, 40, 1), (33, 52, 3),
